@@ -676,6 +676,44 @@ def write_detail(out):
     return DETAIL_FILE
 
 
+DUMP_BUDGET = 64 << 20                    # bytes of .npy payload --dump-outputs may write in all
+DUMP_SEED = 20260917
+
+
+def dump_outputs(job, out_dir):
+    """--dump-outputs DIR: what the last timed step returned to its caller (job.ez, one ksw_extz_t per pair) as float64 .npy files,
+    so two builds can be compared output for output.  One file per ksw_extz_t field (ksw2_amd.FIELDS, every pair); the CIGARs as
+    cigar.npy (the words of the pairs listed in cigar_pair.npy, concatenated) + cigar_offset.npy.  When every CIGAR does not fit
+    DUMP_BUDGET, the pairs are taken in a fixed seeded order while they fit."""
+    n = job.n
+    C = ksw2_amd.KswExtz
+    raw = np.frombuffer((ctypes.c_char * (ctypes.sizeof(C) * n)).from_buffer(job.ez), dtype=np.dtype(
+        {"names": [f for f, _ in C._fields_], "formats": ["<u4"] + ["<i4"] * 10 + ["<u8"],
+         "offsets": [getattr(C, f).offset for f, _ in C._fields_], "itemsize": ctypes.sizeof(C)}))
+    cols = {f: raw[f] for f in ("max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score", "n_cigar", "reach_end")}
+    cols["max"], cols["zdropped"] = raw["max_zd"] & 0x7fffffff, raw["max_zd"] >> 31
+    os.makedirs(out_dir, exist_ok=True)
+    for f in ksw2_amd.FIELDS:
+        np.save(os.path.join(out_dir, f + ".npy"), cols[f].astype(np.float64))
+    ncig = np.maximum(raw["n_cigar"], 0).astype(np.int64)
+    if not ncig.any():
+        return
+    room = DUMP_BUDGET // 8 - len(ksw2_amd.FIELDS) * n - 2 * (n + 1)          # float64 words left for CIGAR words + pair list + offsets
+    if int(ncig.sum()) <= room:
+        pairs = np.arange(n)
+    else:
+        order = np.random.Generator(np.random.PCG64(DUMP_SEED)).permutation(n)
+        pairs = np.sort(order[np.cumsum(ncig[order]) <= room])
+    off = np.concatenate([[0], np.cumsum(ncig[pairs])])
+    words = np.empty(int(off[-1]), dtype=np.float64)
+    for k, i in enumerate(pairs):
+        if ncig[i]:
+            words[off[k]:off[k + 1]] = np.ctypeslib.as_array(job.ez[i].cigar, shape=(int(ncig[i]),))
+    np.save(os.path.join(out_dir, "cigar.npy"), words)
+    np.save(os.path.join(out_dir, "cigar_pair.npy"), pairs.astype(np.float64))
+    np.save(os.path.join(out_dir, "cigar_offset.npy"), off.astype(np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -699,7 +737,13 @@ def main():
     ap.add_argument("--resident-only", action="store_true", help="profiling: only the HBM-resident kernel loop (what rocprofv3 should see)")
     ap.add_argument("--approx", action="store_true", help="OR KSW_EZ_APPROX_MAX into the flags (score + corner CIGAR only, as in the reference)")
     ap.add_argument("--sse-compat", action="store_true", help="OR KSW2AMD_EZ_SSE_COMPAT into the flags: the SSE kernels' own results through the SSE-compatible kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline returned (rank 0's pairs) to DIR/<name>.npy, float64, <= 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.resident_only:
+        ap.error("--dump-outputs needs the timed batch entry point; --resident-only skips it")
 
     # N > 1 without a launcher: start our own ranks BEFORE anything touches a GPU (a process that has initialised HIP is never
     # re-exec'ed); the child ranks print the JSON line, we pass their exit code on
@@ -777,6 +821,8 @@ def main():
     dt = time.perf_counter() - t0
     stats1 = lib.host_stats()
     phase1 = lib.host_phase_ms()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
     # host-thread milliseconds per step of this rank's batch entry calls (summed over its worker threads): plan creation = pack / gather /
     # uploads issued; launch calls; waiting for the device + fetch + ksw_extz_t assembly.  In config.per_rank: which side a slow rank was slow on.
     host_ms = {k: round((phase1[k] - phase0[k]) / max(args.steps, 1), 3) for k in ("create_ms", "launch_ms", "wait_fetch_ms")}

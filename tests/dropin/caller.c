@@ -1,5 +1,5 @@
 /* A ksw2 caller exactly as it would be written against the reference: it includes the REFERENCE's own ksw2.h
- * (-I/root/reference at compile time; the file is not copied) and is linked against libksw2_amd (here: the simulator
+ * (-I/root/reference at compile time, `make -C oracle dropin` in build(); the file is not copied) and is linked against libksw2_amd (here: the simulator
  * build, so the test runs without a GPU).  Reads pairs from stdin: "<algo> <w> <zdrop> <flag> <query> <target>" with
  * ACGTN strings, prints the ksw_extz_t fields and the CIGAR; tests/test_dropin_header.py compares with the oracle. */
 #include <stdio.h>

@@ -97,6 +97,53 @@ def test_bench_two_ranks_plumbing(sim, tmp_path):
     assert full["value"] == d["value"] and "kernels" in full["roofline"] and "parity_detail" in full
 
 
+def test_dump_outputs_is_what_the_last_step_returned(sim, tmp_path, monkeypatch):
+    """--dump-outputs: every ksw_extz_t field of every pair and the CIGARs, as float64; over budget, a seeded subset of whole CIGARs."""
+    wl = dict(bench.WORKLOADS["cfg3"], qlen=300, tlen=300, w=40)
+    j = bench.Job(sim, "cfg3", wl, 0, n_override=6)
+    j.e2e_step()
+    got = [ka.ez_to_dict(j.ez[i]) for i in range(j.n)]
+    bench.dump_outputs(j, str(tmp_path / "all"))
+    for f in ka.FIELDS:
+        a = np.load(str(tmp_path / "all" / (f + ".npy")))
+        assert a.dtype == np.float64 and a.tolist() == [g[f] for g in got], f
+    pairs, off, words = (np.load(str(tmp_path / "all" / (f + ".npy"))) for f in ("cigar_pair", "cigar_offset", "cigar"))
+    assert pairs.tolist() == list(range(j.n)) and sum(g["n_cigar"] for g in got) > 0
+    assert all(words[int(off[k]):int(off[k + 1])].tolist() == got[k]["cigar"] for k in range(j.n))
+    small = len(ka.FIELDS) * j.n + 2 * (j.n + 1) + sum(g["n_cigar"] for g in got) // 2
+    monkeypatch.setattr(bench, "DUMP_BUDGET", small * 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(j, str(tmp_path / d))
+    pairs, off, words = (np.load(str(tmp_path / "a" / (f + ".npy"))) for f in ("cigar_pair", "cigar_offset", "cigar"))
+    assert 0 < len(pairs) < j.n and (np.diff(pairs) > 0).all() and len(words) * 8 <= small * 8
+    assert all(words[int(off[k]):int(off[k + 1])].tolist() == got[int(p)]["cigar"] for k, p in enumerate(pairs))
+    assert all((np.load(str(tmp_path / "a" / f)) == np.load(str(tmp_path / "b" / f))).all() for f in os.listdir(str(tmp_path / "a")))
+    j.free_ez()
+
+
+def test_bench_dump_outputs_repeat(sim, tmp_path):
+    """`python bench.py --gpus 1 ... --dump-outputs DIR` on the simulator build: the same arguments give the same inputs, hence the
+    same dumped outputs, run after run; `steps` and `ms_per_step` are in the line."""
+    import json
+    import sys
+    root = os.path.dirname(SIM_DIR.rstrip("/")).rsplit("/tests", 1)[0]
+    env = dict(os.environ, KSW2_BENCH_PLUMBING_LIB=os.path.join(SIM_DIR, "libksw2_amd_sim.so"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg3", "--pairs", "12",
+                            "--no-cpu", "--no-also", "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b"))) and {f + ".npy" for f in ka.FIELDS + ["cigar"]} <= set(names)
+    for f in names:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    assert len(np.load(str(tmp_path / "a" / "score.npy"))) == 12
+
+
 def test_recorded_traffic_names_the_latest_profile_of_the_same_workload():
     """`roofline.traffic` replays the PMC summary under profiles/ whose name sorts last for exactly this workload: records of
     attempts that were not kept (another kernel) carry another workload tag and must not be picked up."""

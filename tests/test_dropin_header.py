@@ -1,5 +1,6 @@
 """CPU: a caller compiled against the REFERENCE's own ksw2.h links and runs against our library unchanged (struct layout,
-prototypes, flag values, CIGAR ownership).  Needs /root/reference at compile time only; linked against the simulator build."""
+prototypes, flag values, CIGAR ownership).  The callers are compiled by build() (`make -C oracle dropin`, oracle/_ref/) where the
+reference's sources exist, and linked against the simulator build."""
 import os
 import subprocess
 
@@ -11,20 +12,16 @@ from oracle import pyoracle as po
 from tests import golden_util as gu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+CALLER = os.path.join(ROOT, "oracle", "_ref", "dropin-caller")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "ksw2.h")), reason="reference header not present")
+@pytest.mark.skipif(not os.path.exists(CALLER), reason="oracle/_ref/dropin-caller not built (needs the reference's sources at build time)")
 @pytest.mark.parametrize("kalloc", [False, True])
-def test_caller_built_against_reference_header(tmp_path, kalloc):
+def test_caller_built_against_reference_header(kalloc):
     """kalloc=True: the caller is built with -DHAVE_KALLOC plus the reference's kalloc.c (compiled where it lies) and passes
     its pool as `km`; the library finds the process's krealloc (executable linked with -rdynamic) and grows the CIGAR there."""
-    sim_dir = os.path.join(ROOT, "tests", "sim")
-    subprocess.run(["make", "-C", sim_dir], check=True, capture_output=True)
-    exe = str(tmp_path / "caller")
-    extra = ["-DHAVE_KALLOC", os.path.join(REF, "kalloc.c"), "-rdynamic"] if kalloc else []
-    subprocess.run(["gcc", "-O1", "-Wall", "-I" + REF, os.path.join(ROOT, "tests", "dropin", "caller.c")] + extra + ["-o", exe,
-                    "-L" + sim_dir, "-lksw2_amd_sim", "-Wl,-rpath," + sim_dir], check=True, capture_output=True)
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "sim")], check=True, capture_output=True)
+    exe = CALLER + ("-kalloc" if kalloc else "")
     rng = np.random.Generator(np.random.PCG64(12))
     mat = synth.simple_mat(5, 2, 4, -1)
     lines, expect = [], []
