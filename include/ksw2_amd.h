@@ -129,6 +129,19 @@ void ksw_exts2_sse2(void *km, int qlen, const uint8_t *query, int tlen, const ui
 void ksw_extf2_sse(void *km, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int8_t mch, int8_t mis, int8_t e, int w, int xdrop,
                    ksw_extz_t *ez);
 
+/* (ksw2.h:92-93) local alignment; the reference declares this pair but never defines it, so the contract is this library's
+ * (DESIGN.md section 3.14): the best Smith-Waterman score of the query against the target over the full, unbanded matrix, with
+ * s(t, q) = mat[t * m + q] and a gap of length l costing gapo + l * gape.  *qe / *te = 0-based query / target index of the best
+ * cell; ties go to the smallest te, then the smallest qe; a best score of 0 (or qlen <= 0, tlen <= 0) returns 0 with *qe = *te = -1.
+ * Exact int32 arithmetic: unlike a 16-bit SSE implementation, scores above 32767 do not saturate (the one intended difference from
+ * the name).  m 1..127, gapo / gape 0..127, every residue code < m; size (1 or 2) is stored and changes nothing.
+ * ksw_ll_qinit returns ONE block from km (NULL: malloc; free with free() / kfree(km, q)) holding copies of query and mat -- the caller
+ * may free its buffers afterwards; no device state.  Bad arguments: NULL, ksw2amd_last_error() says why.
+ * ksw_ll_i16 on a device failure or a bad argument returns 0 with *qe = *te = -1 and reports like the void entry points above
+ * (ksw2amd_error_count, ksw2amd_last_error, the error handler, KSW2AMD_ABORT_ON_ERROR). */
+void *ksw_ll_qinit(void *km, int size, int qlen, const uint8_t *query, int m, const int8_t *mat);
+int ksw_ll_i16(void *q, int tlen, const uint8_t *target, int gapo, int gape, int *qe, int *te);
+
 /* ------------------------------------------------------------------ Part 2: batched front-end */
 
 /* scoring shared by every pair of a batch (the arguments m, mat, q, e[, q2, e2] of the calls above) */
@@ -259,6 +272,20 @@ int ksw2amd_extf_batch(void *km, int8_t mch, int8_t mis, int8_t e, int n, const 
  * nothing of them crosses the link.  (Replaces nothing in the reference: ksw2.h has no notion of a device.) */
 int ksw2amd_exts_batch_device(void *km, const ksw2amd_splice_t *sc, int n, const ksw2amd_spair_t *pairs, ksw_extz_t *ez);
 int ksw2amd_extf_batch_device(void *km, int8_t mch, int8_t mis, int8_t e, int n, const ksw2amd_fpair_t *pairs, ksw_extz_t *ez);
+
+/* local-alignment batches (ksw_ll_i16 above, many pairs per launch): res[i] is what
+ *   ksw_ll_i16(ksw_ll_qinit(0, 2, pairs[i].qlen, pairs[i].query, m, mat), pairs[i].tlen, pairs[i].target, gapo, gape, &qe, &te)
+ * returns (score, qe, te).  Every argument and every residue code is checked before anything runs: KSW2AMD_E_PARAM, no launch.
+ * Pairs of the same shape whose best score provably fits 16 bits run two per wavefront in packed 16-bit arithmetic, the others in
+ * int32; the results are the same. */
+typedef struct {
+	const uint8_t *query, *target;
+	int32_t qlen, tlen;
+} ksw2amd_lpair_t;
+typedef struct {
+	int32_t score, qe, te;
+} ksw2amd_lres_t;
+int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

@@ -50,6 +50,16 @@ class LinearPair(ctypes.Structure):
                 ("w", ctypes.c_int32), ("xdrop", ctypes.c_int32)]
 
 
+class LocalPair(ctypes.Structure):
+    """ksw2amd_lpair_t: one local alignment of ksw2amd_ll_batch."""
+    _fields_ = [("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("tlen", ctypes.c_int32)]
+
+
+class LocalResult(ctypes.Structure):
+    """ksw2amd_lres_t: score, qe, te."""
+    _fields_ = [("score", ctypes.c_int32), ("qe", ctypes.c_int32), ("te", ctypes.c_int32)]
+
+
 class Pair(ctypes.Structure):
     _fields_ = [("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("tlen", ctypes.c_int32),
                 ("w", ctypes.c_int32), ("zdrop", ctypes.c_int32), ("end_bonus", ctypes.c_int32), ("flag", ctypes.c_int32)]
@@ -81,14 +91,16 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_set_sse_compat", "ksw2amd_sse_plan_create", "ksw2amd_plan_describe", "ksw2amd_reload_env",
            "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat", "ksw2amd_host_register", "ksw2amd_host_unregister",
            "ksw2amd_device_alloc", "ksw2amd_device_free", "ksw2amd_device_upload", "ksw2amd_device_download", "ksw2amd_rerun_count",
-           "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device"]
+           "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device",
+           "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
                 "ksw_extz2_sse2", "ksw_extd2_sse41", "ksw_extd2_sse2", "ksw_exts2_sse", "ksw_exts2_sse41", "ksw_exts2_sse2", "ksw_extf2_sse",
                 "ksw2amd_extz_batch", "ksw2amd_extd_batch", "ksw2amd_exts_batch", "ksw2amd_extf_batch", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device", "ksw2amd_plan_create",
                 "ksw2amd_sse_plan_create", "ksw2amd_exts_plan_create", "ksw2amd_extf_plan_create", "ksw2amd_plan_run",
-                "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat"]
+                "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
+                "ksw_ll_i16", "ksw2amd_ll_batch"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -213,8 +225,14 @@ class Library:
                 reload_env()
                 return fn(*a)
             return call
+        if hasattr(L, "ksw2amd_ll_batch"):          # (the simulator build of tests/sim has no local alignment)
+            L.ksw_ll_qinit.argtypes = [km, _int, _int, _u8p, _int, _i8p]
+            L.ksw_ll_qinit.restype = ctypes.c_void_p
+            L.ksw_ll_i16.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+            L.ksw2amd_ll_batch.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
         for name in _ENV_ENTRIES:
-            setattr(L, name, with_env(getattr(L, name)))
+            if hasattr(L, name):
+                setattr(L, name, with_env(getattr(L, name)))
 
     # ---- info
     def backend(self):
@@ -339,6 +357,41 @@ class Library:
         ez = KswExtz()
         self.lib.ksw_extf2_sse(None, len(qa), qp, len(ta), tp, mch, mis, e, w, xdrop, ez)
         return ez_to_dict(ez, free_cigar=True)
+
+    def ll_batch(self, queries, targets, mat, gapo, gape, m=None):
+        """ksw2amd_ll_batch: best local (Smith-Waterman) score and end cell of every pair -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        n = len(queries)
+        if len(targets) != n:
+            raise ValueError("queries and targets differ in length")
+        keep = [np.ascontiguousarray(x, dtype=np.uint8) for x in list(queries) + list(targets)]
+        pairs = (LocalPair * max(n, 1))()
+        for i in range(n):
+            qa, ta = keep[i], keep[n + i]
+            pairs[i].query, pairs[i].target = qa.ctypes.data, ta.ctypes.data
+            pairs[i].qlen, pairs[i].tlen = len(qa), len(ta)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_ll_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, n, pairs,
+                                       out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def ll_i16(self, query, target, mat, gapo, gape, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw_ll_i16; the profile is released with libc free() -> (score, qe, te)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        qa, qp = self._seq(query)
+        ta, tp = self._seq(target)
+        prof = self.lib.ksw_ll_qinit(None, size, len(qa), qp, m, mat.ctypes.data_as(_i8p))
+        if not prof:
+            raise Ksw2Error("ksw_ll_qinit: " + self.last_error())
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw_ll_i16(prof, len(ta), tp, gapo, gape, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

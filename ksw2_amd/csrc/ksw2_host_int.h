@@ -50,6 +50,8 @@
 	X(EXTS_REG) \
 	X(LDSCODES) \
 	X(LDSROWS) \
+	X(LL_FORM) \
+	X(LL_LDS) \
 	X(LONG_MS) \
 	X(MAX_BYTES) \
 	X(NO_PARCOPY) \
@@ -278,6 +280,7 @@ int64_t now_ns(void);
 int trace_on(void);
 int run_pooled(chunk_fn fn, void *ctx, int n, const double *cost, double total, int nchunks, int chunk_pairs, int *rc);
 void call_failed(const char *fn, int code, ksw_extz_t *ez);
+void *km_realloc(void *km, void *p, size_t size);
 void env_load(void);
 size_t thread_cached_device_bytes(void);
 void *shared_upload_stream(void);

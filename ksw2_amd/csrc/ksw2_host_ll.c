@@ -1,0 +1,231 @@
+/*
+ * ksw2_host_ll.c -- local alignment (ksw2.h:92-93): ksw_ll_qinit / ksw_ll_i16 and the batch entry ksw2amd_ll_batch.
+ *
+ * The reference declares the pair and never defines it; the contract is this library's own (include/ksw2_amd.h, DESIGN.md section
+ * 3.14): the best Smith-Waterman score over the full matrix, its cell (largest score, then smallest te, then smallest qe), exact int32.
+ * Host side of the batch, modelled on the extf batch path: validate every pair, sort, stage every sequence into one pinned arena with
+ * the task table and the pen tables, one upload, one launch per kernel form, one 12-byte-per-pair download.  Kernels: ksw2_lane_ll.h.
+ *
+ * This is the only host object that calls k2a_shim_launch_ll (tests/sim links the other four against a simulator without it).
+ */
+#include "ksw2_host_int.h"
+
+/* the packed form is exact while no H + smax exceeds 65535 (ksw2_lane_ll.h).  A local alignment's best score is at most smax per
+ * aligned pair of residues, i.e. min(qlen, tlen) * smax, so (min(qlen, tlen) + 1) * smax <= 65535 bounds every H + smax; columns
+ * (the shorter length) must also fit the 16-bit column index of the row maxima. */
+static int ll_pk_admit(int qlen, int tlen, int smax)
+{
+	const int64_t mn = imin(qlen, tlen);
+	return (mn + 1) * (int64_t)smax <= 65535 && mn <= 65535;
+}
+
+typedef struct { int32_t rows, cols, sw; uint32_t idx; int64_t cost; } ll_sort_t;      /* sw: rows = the query (part of a packed task's shape) */
+static int cmp_shape(const void *a_, const void *b_)
+{
+	const ll_sort_t *a = (const ll_sort_t*)a_, *b = (const ll_sort_t*)b_;
+	if (a->rows != b->rows) return a->rows > b->rows ? -1 : 1;
+	if (a->cols != b->cols) return a->cols > b->cols ? -1 : 1;
+	if (a->sw != b->sw) return a->sw < b->sw ? -1 : 1;
+	return a->idx < b->idx ? -1 : a->idx > b->idx;
+}
+static int cmp_cost(const void *a_, const void *b_)
+{
+	const ll_sort_t *a = (const ll_sort_t*)a_, *b = (const ll_sort_t*)b_;
+	if (a->cost != b->cost) return a->cost > b->cost ? -1 : 1;
+	return a->idx < b->idx ? -1 : a->idx > b->idx;
+}
+
+static int ll_check_args(int m, const int8_t *mat, int gapo, int gape)
+{
+	if (m < 1 || m > K2A_MAXM) return fail(KSW2AMD_E_PARAM, "local alignment: m must be 1..127%s", "");
+	if (!mat) return fail(KSW2AMD_E_PARAM, "local alignment: mat is NULL%s", "");
+	if (gapo < 0 || gapo > 127 || gape < 0 || gape > 127) return fail(KSW2AMD_E_PARAM, "local alignment: gapo and gape must be 0..127%s", "");
+	return KSW2AMD_OK;
+}
+
+static int ll_bad_code(const uint8_t *s, int len, int m)
+{
+	int i;
+	for (i = 0; i < len; ++i) if (s[i] >= m) return 1;
+	return 0;
+}
+
+/* one chunk: pairs [0, n) of the caller's, all validated */
+static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
+{
+	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
+	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
+	const int lds = m > 5 || env_flag(lv, 0);
+	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
+	K2aLLTask *tk = 0;
+	uint8_t *h_arena = 0, *d_arena = 0, *d_scr = 0;
+	K2aLLRes *h_res = 0, *d_res = 0;
+	size_t cap_h = 0, cap_d = 0, cap_s = 0, cap_hr = 0, cap_dr = 0;
+	int npk = 0, ni32 = 0, ntk_pk = 0, ntk = 0, i, rc = KSW2AMD_OK;
+	size_t tab_off, seq_off, bytes, scr = 0;
+	void *st = thread_stream();
+	if (!pk || !i32) { free(pk); free(i32); return fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); }
+	for (i = 0; i < n; ++i) {
+		const ksw2amd_lpair_t *p = &pairs[i];
+		ll_sort_t s;
+		res[i].score = 0; res[i].qe = res[i].te = -1;
+		if (p->qlen <= 0 || p->tlen <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
+		s.rows = imax(p->qlen, p->tlen); s.cols = imin(p->qlen, p->tlen); s.sw = p->qlen > p->tlen; s.idx = (uint32_t)i;
+		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
+		if (form > 0 && ll_pk_admit(p->qlen, p->tlen, smax)) pk[npk++] = s;
+		else i32[ni32++] = s;
+	}
+	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
+	qsort(pk, (size_t)npk, sizeof(ll_sort_t), cmp_shape);
+	{	/* pairs from the back of the array to its front (entries n + 1 .. 2 n + 1 are free): a task can take two slots for one entry */
+		int k = 0, w = 0;
+		memmove(pk + n + 1, pk, sizeof(ll_sort_t) * (size_t)npk);
+		while (k < npk) {
+			const ll_sort_t *a = &pk[n + 1 + k];
+			if (k + 1 < npk && a[1].rows == a[0].rows && a[1].cols == a[0].cols && a[1].sw == a[0].sw) { pk[w++] = a[0]; pk[w++] = a[1]; k += 2; }
+			else if (form == 2) { pk[w++] = a[0]; pk[w++] = a[0]; k += 1; }
+			else { i32[ni32++] = a[0]; k += 1; }
+		}
+		npk = w;
+	}
+	ntk_pk = npk / 2;
+	qsort(pk, (size_t)ntk_pk, 2 * sizeof(ll_sort_t), cmp_cost);        /* tasks (pairs of entries) longest first */
+	qsort(i32, (size_t)ni32, sizeof(ll_sort_t), cmp_cost);
+	ntk = ntk_pk + ni32;
+	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers");
+	if (ntk == 0) { free(pk); free(i32); return KSW2AMD_OK; }
+	/* arena: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once) */
+	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
+	seq_off = tab_off + align_up((size_t)2 * m * m, 256);
+	bytes = seq_off;
+	for (i = 0; i < npk; ++i) if (i % 2 == 0 || pk[i].idx != pk[i - 1].idx) bytes += align_up((size_t)pk[i].rows, 4) + align_up((size_t)pk[i].cols, 4);
+	for (i = 0; i < ni32; ++i) bytes += align_up((size_t)i32[i].rows, 4) + align_up((size_t)i32[i].cols, 4);
+	h_arena = (uint8_t*)cache_get(BUF_HSEQ, bytes, &cap_h);
+	d_arena = (uint8_t*)cache_get(BUF_SEQ, bytes, &cap_d);
+	h_res = (K2aLLRes*)cache_get(BUF_HRES, sizeof(K2aLLRes) * (size_t)n, &cap_hr);
+	d_res = (K2aLLRes*)cache_get(BUF_RES, sizeof(K2aLLRes) * (size_t)n, &cap_dr);
+	if (!h_arena || !d_arena || !h_res || !d_res) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: buffer allocation failed: %s", k2a_shim_last_error()); goto out; }
+	tk = (K2aLLTask*)h_arena;
+	{
+		uint8_t *tab = h_arena + tab_off;
+		size_t off = seq_off;
+		int t, a, b;
+		for (a = 0; a < m; ++a)
+			for (b = 0; b < m; ++b) {
+				tab[a * m + b] = (uint8_t)(smax - mat[a * m + b]);             /* rows = target: pen(t, q) */
+				tab[m * m + a * m + b] = (uint8_t)(smax - mat[b * m + a]);     /* rows = query:  pen(q, t) */
+			}
+		for (t = 0; t < ntk; ++t) {
+			const int is_pk = t < ntk_pk;
+			K2aLLTask *k = &tk[t];
+			int h;
+			memset(k, 0, sizeof(*k));
+			for (h = 0; h < (is_pk ? 2 : 1); ++h) {
+				const ll_sort_t *s = is_pk ? &pk[2 * t + h] : &i32[t - ntk_pk];
+				const ksw2amd_lpair_t *p = &pairs[s->idx];
+				const int sw = p->qlen > p->tlen;                          /* rows = the longer sequence; the target on equal lengths */
+				const uint8_t *rs = sw ? p->query : p->target, *cs = sw ? p->target : p->query;
+				k->nrows = s->rows; k->ncols = s->cols; k->swapped = sw;
+				k->res[h] = s->idx;
+				if (h == 1 && s->idx == k->res[0]) { k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; continue; }
+				k->roff[h] = (uint32_t)off; memcpy(h_arena + off, rs, (size_t)s->rows); off += align_up((size_t)s->rows, 4);
+				k->coff[h] = (uint32_t)off; memcpy(h_arena + off, cs, (size_t)s->cols); off += align_up((size_t)s->cols, 4);
+			}
+			if (!is_pk) { k->res[1] = k->res[0]; k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; }
+			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * 8, 256); }
+		}
+	}
+	if (scr) {
+		d_scr = (uint8_t*)cache_get(BUF_TB, scr, &cap_s);
+		if (!d_scr) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: scratch allocation failed: %s", k2a_shim_last_error()); goto out; }
+	}
+	{
+		K2aLL par;
+		par.m = m; par.smax = smax; par.oe = gapo + gape; par.ge = gape;
+		if (k2a_shim_h2d(d_arena, h_arena, bytes, st)
+		    || k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_arena, d_arena + tab_off, d_scr, d_res, st)
+		    || k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_arena, d_arena + tab_off, d_scr, d_res, st)
+		    || k2a_shim_d2h(h_res, d_res, sizeof(K2aLLRes) * (size_t)n, st)
+		    || k2a_shim_stream_sync(st)) { rc = fail(KSW2AMD_E_NODEVICE, "local alignment: %s", k2a_shim_last_error()); goto out; }
+	}
+	for (i = 0; i < npk; ++i) { const K2aLLRes *r = &h_res[pk[i].idx]; res[pk[i].idx].score = r->score; res[pk[i].idx].qe = r->qe; res[pk[i].idx].te = r->te; }
+	for (i = 0; i < ni32; ++i) { const K2aLLRes *r = &h_res[i32[i].idx]; res[i32[i].idx].score = r->score; res[i32[i].idx].qe = r->qe; res[i32[i].idx].te = r->te; }
+out:
+	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
+	if (h_arena) cache_put(BUF_HSEQ, h_arena, cap_h);
+	if (d_arena) cache_put(BUF_SEQ, d_arena, cap_d);
+	if (h_res) cache_put(BUF_HRES, h_res, cap_hr);
+	if (d_res) cache_put(BUF_RES, d_res, cap_dr);
+	free(pk); free(i32);
+	return rc;
+}
+
+int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
+{
+	int i, rc, beg = 0, smax = -128;
+	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
+	if (n < 0 || (n > 0 && (!pairs || !res))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */
+		const ksw2amd_lpair_t *p = &pairs[i];
+		char msg[96];
+		if ((p->qlen > 0 && !p->query) || (p->tlen > 0 && !p->target)) { snprintf(msg, sizeof(msg), "%d", i); return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: NULL sequence", msg); }
+		if ((p->qlen > 0 && ll_bad_code(p->query, p->qlen, m)) || (p->tlen > 0 && ll_bad_code(p->target, p->tlen, m))) {
+			snprintf(msg, sizeof(msg), "%d", i);
+			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: residue code >= m", msg);
+		}
+	}
+	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
+	if (n == 0) return KSW2AMD_OK;
+	if (smax > 0 && k2a_shim_device_count() <= 0) return fail(KSW2AMD_E_NODEVICE, "no usable %s device", k2a_shim_backend());
+	while (beg < n) {                                       /* chunks of up to ~3 GB of arena + boundary scratch */
+		size_t b = 0;
+		int end;
+		for (end = beg; end < n; ++end) {
+			const size_t rows = (size_t)imax(imax(pairs[end].qlen, pairs[end].tlen), 0), cols = (size_t)imax(imin(pairs[end].qlen, pairs[end].tlen), 0);
+			const size_t pb = rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0);
+			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
+			b += pb;
+		}
+		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, pairs + beg, res + beg);
+		if (rc) return rc;
+		beg = end;
+	}
+	return KSW2AMD_OK;
+}
+
+/* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */
+typedef struct {
+	int32_t size, qlen, m, pad;      /* then qlen query codes, then m * m matrix entries */
+} ll_prof_t;
+
+void *ksw_ll_qinit(void *km, int size, int qlen, const uint8_t *query, int m, const int8_t *mat)
+{
+	const int ql = imax(qlen, 0);
+	ll_prof_t *p;
+	if (size != 1 && size != 2) { fail(KSW2AMD_E_PARAM, "ksw_ll_qinit: size must be 1 or 2%s", ""); return 0; }
+	if (m < 1 || m > K2A_MAXM || !mat) { fail(KSW2AMD_E_PARAM, "ksw_ll_qinit: m must be 1..127 and mat non-NULL%s", ""); return 0; }
+	if (ql > 0 && (!query || ll_bad_code(query, ql, m))) { fail(KSW2AMD_E_PARAM, "ksw_ll_qinit: query NULL or a residue code >= m%s", ""); return 0; }
+	p = (ll_prof_t*)km_realloc(km, 0, sizeof(ll_prof_t) + (size_t)ql + (size_t)m * m);
+	if (!p) { fail(KSW2AMD_E_NOMEM, "ksw_ll_qinit: allocation failed%s", ""); return 0; }
+	p->size = size; p->qlen = qlen; p->m = m; p->pad = 0;
+	if (ql > 0) memcpy((uint8_t*)(p + 1), query, (size_t)ql);
+	memcpy((uint8_t*)(p + 1) + ql, mat, (size_t)m * m);
+	return p;
+}
+
+int ksw_ll_i16(void *q, int tlen, const uint8_t *target, int gapo, int gape, int *qe, int *te)
+{
+	const ll_prof_t *p = (const ll_prof_t*)q;
+	ksw2amd_lpair_t pr;
+	ksw2amd_lres_t r;
+	int rc;
+	if (qe) *qe = -1;
+	if (te) *te = -1;
+	if (!p) { rc = fail(KSW2AMD_E_PARAM, "ksw_ll_i16: NULL profile%s", ""); call_failed("ksw_ll_i16", rc, 0); return 0; }
+	pr.query = (const uint8_t*)(p + 1); pr.qlen = p->qlen; pr.target = target; pr.tlen = tlen;
+	rc = ksw2amd_ll_batch(p->m, (const int8_t*)(p + 1) + imax(p->qlen, 0), gapo, gape, 1, &pr, &r);
+	if (rc != KSW2AMD_OK) { call_failed("ksw_ll_i16", rc, 0); return 0; }
+	if (qe) *qe = r.qe;
+	if (te) *te = r.te;
+	return r.score;
+}

@@ -310,6 +310,7 @@ static void *cigar_realloc(void *km, void *p, size_t size)
 	}
 	return kr(km, p, size);
 }
+void *km_realloc(void *km, void *p, size_t size) { return cigar_realloc(km, p, size); }      /* the same hook for ksw_ll_qinit's profile */
 
 void ez_reset(ksw_extz_t *ez)           /* ksw2.h:184-189; cigar and m_cigar survive */
 {

@@ -1,0 +1,198 @@
+/*
+ * ksw2_lane_ll.h -- per-lane code of the local-alignment kernels (ksw_ll_i16 / ksw2amd_ll_batch, ksw2.h:92-93), shared by the gfx950
+ * kernel (ksw2_shim_hip.hip) and the lock-step simulator of the tests (tests/llsim).
+ *
+ * Contract: H(i,j) = max(0, H(i-1,j-1) + s(t_i, q_j), E(i,j), F(i,j)) with Gotoh E / F, a gap of length l
+ * costing gapo + l * gape, over the full unbanded matrix; the result is the largest H and its cell, ties broken by the smallest
+ * target index, then the smallest query index; a best score of 0 reports (-1, -1).
+ *
+ * Every value of a local alignment is >= 0, so E and F are held clamped at 0: H = max(0, ...) does not change, and the boundary
+ * (row -1, column -1) is all zeros.  Two number formats share the schedule:
+ *   int32 (PK = false): one alignment per wavefront, exact for any length;
+ *   packed (PK = true): two alignments of the same shape per wavefront, one per 16-bit half of every register, in unsigned
+ *     saturating arithmetic (v_pk_add_u16 / v_pk_sub_u16 with clamp, v_pk_max_u16).  Exact as long as H + smax never exceeds
+ *     65535: the host admits a pair only when (min(qlen, tlen) + 1) * smax <= 65535 (ksw2_host_ll.c, ll_pk_admit).
+ *
+ * Schedule (the strip schedule of ksw2_lane.h without a band): rows are the longer sequence, cut into generations of 64 strips of
+ * C rows; lane l owns strip l of a generation and walks the columns one per step, skewed by l steps, so the bottom row's (H, E) of
+ * strip l reaches lane l + 1 by one DPP rotate per value and step.  Lane 63's bottom row goes to a per-task boundary in HBM
+ * (8 bytes per column) that lane 0 reads in the next generation.  Generations run one after the other: 63 idle lane-steps per
+ * generation and lane, and every lane changes strips at the same step.
+ *
+ * Maximum: every row keeps its largest H and the first column that reached it (strict >, columns ascending); at the end of a
+ * generation the rows are folded into the lane's key (score, -te, -qe), and the 64 keys are reduced once per task.
+ *
+ * Scores come from pen = smax - s, a byte per (row code, column code): with m <= 5 from two (int32) or three (packed) registers
+ * per row built at the start of a generation and one v_perm_b32 per row and step ("column profile"); for any m up to 127 from a
+ * table in LDS (one ds_read_u8 per row, alignment and step).
+ */
+#ifndef KSW2_LANE_LL_H_
+#define KSW2_LANE_LL_H_
+
+#include "ksw2_lane.h"
+
+/* ---- packed 16-bit helpers: a uint32 holds two unsigned halves */
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned short k2a_ll_u16x2 __attribute__((ext_vector_type(2)));
+K2A_FN k2a_ll_u16x2 k2a_ll_h2(uint32_t a) { return __builtin_bit_cast(k2a_ll_u16x2, a); }
+K2A_FN uint32_t k2a_ll_w2(k2a_ll_u16x2 a) { return __builtin_bit_cast(uint32_t, a); }
+K2A_FN uint32_t k2a_ll_adds(uint32_t a, uint32_t b) { return k2a_ll_w2(__builtin_elementwise_add_sat(k2a_ll_h2(a), k2a_ll_h2(b))); }
+K2A_FN uint32_t k2a_ll_subs(uint32_t a, uint32_t b) { return k2a_ll_w2(__builtin_elementwise_sub_sat(k2a_ll_h2(a), k2a_ll_h2(b))); }
+K2A_FN uint32_t k2a_ll_max(uint32_t a, uint32_t b) { return k2a_ll_w2(__builtin_elementwise_max(k2a_ll_h2(a), k2a_ll_h2(b))); }
+K2A_FN uint32_t k2a_ll_min(uint32_t a, uint32_t b) { return k2a_ll_w2(__builtin_elementwise_min(k2a_ll_h2(a), k2a_ll_h2(b))); }
+K2A_FN uint32_t k2a_ll_mul(uint32_t a, uint32_t b) { return k2a_ll_w2(k2a_ll_h2(a) * k2a_ll_h2(b)); }
+K2A_FN uint32_t k2a_ll_perm(uint32_t s0, uint32_t s1, uint32_t sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
+#else
+K2A_FN uint32_t k2a_ll_op(uint32_t a, uint32_t b, int op)
+{
+	uint32_t r = 0;
+	for (int h = 0; h < 2; ++h) {
+		const int32_t x = (int32_t)((a >> (16 * h)) & 0xffffu), y = (int32_t)((b >> (16 * h)) & 0xffffu);
+		int32_t v = op == 0 ? x + y : op == 1 ? x - y : op == 2 ? (x > y ? x : y) : op == 3 ? (x < y ? x : y) : (int32_t)((uint32_t)(x * y) & 0xffffu);
+		v = v < 0 ? 0 : v > 0xffff ? 0xffff : v;
+		r |= (uint32_t)v << (16 * h);
+	}
+	return r;
+}
+K2A_FN uint32_t k2a_ll_adds(uint32_t a, uint32_t b) { return k2a_ll_op(a, b, 0); }
+K2A_FN uint32_t k2a_ll_subs(uint32_t a, uint32_t b) { return k2a_ll_op(a, b, 1); }
+K2A_FN uint32_t k2a_ll_max(uint32_t a, uint32_t b) { return k2a_ll_op(a, b, 2); }
+K2A_FN uint32_t k2a_ll_min(uint32_t a, uint32_t b) { return k2a_ll_op(a, b, 3); }
+K2A_FN uint32_t k2a_ll_mul(uint32_t a, uint32_t b) { return k2a_ll_op(a, b, 4); }
+/* v_perm_b32: byte k of the result = byte sel_k of {s0:s1} (s1 = bytes 0-3); selector 12 = 0x00 (the only other one used here) */
+K2A_FN uint32_t k2a_ll_perm(uint32_t s0, uint32_t s1, uint32_t sel)
+{
+	const uint64_t d = ((uint64_t)s0 << 32) | s1;
+	uint32_t r = 0;
+	for (int k = 0; k < 4; ++k) {
+		const uint32_t b = (sel >> (8 * k)) & 0xffu;
+		const uint32_t v = b < 8 ? (uint32_t)(d >> (8 * b)) & 0xffu : b >= 13 ? 0xffu : 0u;
+		r |= v << (8 * k);
+	}
+	return r;
+}
+#endif
+
+/* the lane's best cell so far: larger score, then smaller te, then smaller qe */
+struct K2aLLKey { int s, te, qe; };
+K2A_FN bool k2a_ll_better(int s, int te, int qe, const K2aLLKey &k)
+{
+	return s > k.s || (s == k.s && (te < k.te || (te == k.te && qe < k.qe)));
+}
+K2A_FN void k2a_ll_key_reset(K2aLLKey &k) { k.s = 0; k.te = -1; k.qe = -1; }
+
+/* PK: two alignments per lane (packed form); LDSP: scores from the LDS table (else the register column profile, m <= 5) */
+template<bool PK, bool LDSP>
+struct K2aLaneLL {
+	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
+	int nrows, ncols, swapped, m, lane, i0;
+	uint32_t smax, oe, ge;                     /* packed: the value in both halves */
+	uint32_t hu_prev;                          /* H(i0 - 1, jj - 1): what the lane above delivered one step earlier */
+	uint32_t hl[C], f[C], rmax[C], rcol[C];    /* H(i, jj - 1), F(i, jj), row maximum and its first column */
+	uint32_t pa[C], pb[PK ? C : 1], pw[LDSP ? 1 : C];   /* register profile: pen bytes for column codes 0..3 (pa: low half, pb: high
+	                                                     * half), pw: code 4; LDS profile: pa / pb = row code * m */
+	K2aLLKey key[NH];
+
+	K2A_FN void init(const K2aLL &par, const K2aLLTask &tk, int lane_)
+	{
+		nrows = tk.nrows; ncols = tk.ncols; swapped = tk.swapped; m = par.m; lane = lane_;
+		const uint32_t x = PK ? 0x10001u : 1u;
+		smax = (uint32_t)par.smax * x; oe = (uint32_t)par.oe * x; ge = (uint32_t)par.ge * x;
+		for (int h = 0; h < NH; ++h) k2a_ll_key_reset(key[h]);
+	}
+
+	/* start generation g: this lane's rows, their profile, zeroed columns (tab = the task's pen table in LDS, [row code * m + column code]) */
+	K2A_FN void gen_begin(int g, const uint8_t *r0, const uint8_t *r1, const uint8_t *tab)
+	{
+		i0 = g * K2A_LL_ROWS + lane * C;
+		hu_prev = 0;
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			const int i = i0 + c;
+			const uint32_t a = i < nrows ? r0[i] : 0u, b = (PK && i < nrows) ? r1[i] : 0u;
+			hl[c] = 0; f[c] = 0; rmax[c] = 0; rcol[c] = 0;
+			if (LDSP) {
+				pa[c] = a * (uint32_t)m;
+				if (PK) pb[c] = b * (uint32_t)m;
+			} else {
+				const uint8_t *ta = tab + a * m, *tb = tab + b * m;
+				uint32_t wa = 0, wb = 0, w4 = 0;
+				for (int k = 0; k < 4; ++k) {
+					if (k < m) { wa |= (uint32_t)ta[k] << (8 * k); if (PK) wb |= (uint32_t)tb[k] << (8 * k); }
+				}
+				if (m > 4) w4 = (uint32_t)ta[4] | (PK ? (uint32_t)tb[4] << 16 : 0u);
+				pa[c] = wa;
+				if (PK) pb[c] = wb;
+				if (!LDSP) pw[LDSP ? 0 : c] = w4;
+			}
+		}
+	}
+
+	/* one column jj of the strip.  hin / ein: H(i0 - 1, jj) and E(i0, jj) from the lane above (or the boundary);
+	 * qc: column code (packed: low byte for the low half, next byte for the high half); hout / eout: the same for the lane below */
+	K2A_FN void step(int jj, uint32_t hin, uint32_t ein, uint32_t qc, const uint8_t *tab, uint32_t &hout, uint32_t &eout)
+	{
+		uint32_t hd = hu_prev, e = ein;
+		hu_prev = hin;
+		uint32_t sel = 0, wmask = 0, q0 = qc & 0xffu, q1 = (qc >> 8) & 0xffu;
+		if (!LDSP) {
+			if (PK) {
+				sel = (q0 < 4 ? q0 : 12u) | (12u << 8) | ((q1 < 4 ? 4u + q1 : 12u) << 16) | (12u << 24);
+				wmask = (q0 == 4 ? 0xffffu : 0u) | (q1 == 4 ? 0xffff0000u : 0u);
+			} else sel = q0 | 0x0c0c0c00u;
+		}
+		const uint32_t jj2 = PK ? (uint32_t)jj * 0x10001u : (uint32_t)jj;
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			uint32_t pen;
+			if (LDSP) pen = PK ? (uint32_t)tab[pa[c] + q0] | ((uint32_t)tab[pb[c] + q1] << 16) : (uint32_t)tab[pa[c] + q0];
+			else if (PK) pen = k2a_ll_perm(pb[c], pa[c], sel) | (pw[LDSP ? 0 : c] & wmask);
+			else pen = k2a_ll_perm(pw[LDSP ? 0 : c], pa[c], sel);
+			uint32_t h;
+			if (PK) {
+				h = k2a_ll_max(k2a_ll_max(k2a_ll_subs(k2a_ll_adds(hd, smax), pen), e), f[c]);
+				const uint32_t hoe = k2a_ll_subs(h, oe);
+				e = k2a_ll_max(hoe, k2a_ll_subs(e, ge));
+				f[c] = k2a_ll_max(hoe, k2a_ll_subs(f[c], ge));
+				const uint32_t d = k2a_ll_subs(h, rmax[c]);                           /* > 0 in a half where h is a new row maximum */
+				const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
+				rmax[c] = k2a_ll_max(rmax[c], h);
+				rcol[c] = (jj2 & mask) | (rcol[c] & ~mask);
+			} else {
+				const int t = (int)hd + (int)smax - (int)pen;                          /* e, f >= 0: h >= 0 without a clamp */
+				const int hi = k2a_max(k2a_max(t, (int)e), (int)f[c]);
+				const int hoe = hi - (int)oe;
+				e = (uint32_t)k2a_max3(hoe, (int)e - (int)ge, 0);
+				f[c] = (uint32_t)k2a_max3(hoe, (int)f[c] - (int)ge, 0);
+				h = (uint32_t)hi;
+				if (hi > (int)rmax[c]) { rmax[c] = h; rcol[c] = jj2; }
+			}
+			hd = hl[c];
+			hl[c] = h;
+		}
+		hout = hl[C - 1];
+		eout = e;
+	}
+
+	/* end of a generation: fold the live rows into the lane's key(s).  Every row is looked at (no early exit: the rows past the
+	 * end are masked), and the key is replaced field by field with one condition */
+	K2A_FN void gen_end()
+	{
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			const int i = i0 + c;
+#pragma unroll
+			for (int h = 0; h < NH; ++h) {
+				const int s = (int)(PK ? (rmax[c] >> (16 * h)) & 0xffffu : rmax[c]);
+				const int j = (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
+				const int te = swapped ? j : i, qe = swapped ? i : j;
+				const bool take = i < nrows && s > 0 && k2a_ll_better(s, te, qe, key[h]);
+				key[h].s = take ? s : key[h].s;
+				key[h].te = take ? te : key[h].te;
+				key[h].qe = take ? qe : key[h].qe;
+			}
+		}
+	}
+};
+
+#endif

@@ -169,6 +169,13 @@ int k2a_shim_launch_ssec_trace(const K2aPair *pairs, const uint32_t *order, int 
 int k2a_shim_launch_compact(const K2aPair *pairs, const K2aResult *res, const uint32_t *pos, int n, const uint32_t *cig,
                             uint32_t *pool, void *stream);
 
+/* Local alignment (ksw2_lane_ll.h): one task per wavefront -- an int32 alignment (pk = 0) or two of the same shape in the 16-bit halves
+ * (pk = 1; tasks[t].res[1] == res[0]: one alignment in both).  tab = 2 * m * m pen bytes smax - s (rows = target, then rows = query);
+ * lds = 0 takes the register column profile (m <= 5).  Row / column codes at seq + roff / coff; tasks over K2A_LL_ROWS rows keep their
+ * generation boundary at scratch + boff (8 bytes per column).  res[tasks[t].res[h]] = score, qe, te. */
+int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

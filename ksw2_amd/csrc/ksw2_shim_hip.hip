@@ -20,6 +20,7 @@
 #include "ksw2_lane_ssec.h"
 #include "ksw2_lane_ssecb.h"
 #include "ksw2_lane_extfb.h"
+#include "ksw2_lane_ll.h"
 
 #define K2A_WPB 4          /* wavefronts per workgroup; waves never synchronise with each other */
 /* The traceback walk is a chain of dependent loads and a few dozen instructions per step on ONE lane; what it needs is many
@@ -2165,6 +2166,84 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
 	if (live && gl == 0) k2a_extf_finish(B.bk, B.rdone, B.nr, &res[pi]);
 }
 
+/* ---------------------------------------------------------------- local alignment (ksw2_lane_ll.h)
+ * One task per wavefront (an int32 alignment, or two packed alignments of the same shape), four wavefronts per workgroup that
+ * share the pen tables in LDS: [0, m*m) rows = target, [m*m, 2*m*m) rows = query (swapped tasks).  The per-step inputs of a lane --
+ * its column code(s), and lane 0's boundary entry -- are loaded four steps ahead. */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+              uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	extern __shared__ uint8_t k2a_ll_lds[];
+	const int mm = par.m * par.m;
+	for (int x = threadIdx.x; x < 2 * mm; x += blockDim.x) k2a_ll_lds[x] = tab[x];
+	__syncthreads();
+	const int t = blockIdx.x * K2A_WPB + k2a_wave_id<true>();
+	if (t >= ntasks) return;
+	const int lane = threadIdx.x & 63;
+	const K2aLLTask tk = tasks[t];
+	const uint8_t *ltab = k2a_ll_lds + (tk.swapped ? mm : 0);
+	const uint8_t *r0 = seq + tk.roff[0], *r1 = seq + tk.roff[1 & -(int)PK];
+	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
+	uint2 *bnd = (uint2*)(scratch + tk.boff);
+	const int ncols = tk.ncols, ngen = (tk.nrows + K2A_LL_ROWS - 1) / K2A_LL_ROWS, nsteps = ncols + 63;
+	K2aLaneLL<PK, LDSP> L;
+	L.init(par, tk, lane);
+	for (int g = 0; g < ngen; ++g) {
+		const bool from_bnd = g > 0, to_bnd = g + 1 < ngen;
+		if (from_bnd) {                                /* lane 63's boundary stores of the last generation before lane 0's loads */
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		}
+		L.gen_begin(g, r0, r1, ltab);
+		/* inputs of step k: column code(s) of jj = k - lane (clamped into the sequence), lane 0's boundary entry of column k */
+		uint32_t qc[4], hb[4], eb[4];
+		auto fetch = [&](int k, uint32_t &q, uint32_t &h, uint32_t &e) {
+			const int jj = k2a_min(k2a_max(k - lane, 0), ncols - 1);
+			q = PK ? (uint32_t)c0[jj] | ((uint32_t)c1[jj] << 8) : (uint32_t)c0[jj];
+			h = e = 0;
+			if (lane == 0 && from_bnd) { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
+		};
+#pragma unroll
+		for (int u = 0; u < 4; ++u) fetch(u, qc[u], hb[u], eb[u]);
+		uint32_t hin = 0, ein = 0;
+		for (int k0 = 0; k0 < nsteps; k0 += 4) {
+			uint32_t qn[4], hn[4], en[4];
+#pragma unroll
+			for (int u = 0; u < 4; ++u) fetch(k0 + 4 + u, qn[u], hn[u], en[u]);
+#pragma unroll
+			for (int u = 0; u < 4; ++u) {
+				const int jj = k0 + u - lane;
+				uint32_t ho = 0, eo = 0;
+				if ((unsigned)jj < (unsigned)ncols) {
+					L.step(jj, lane == 0 ? hb[u] : hin, lane == 0 ? eb[u] : ein, qc[u], ltab, ho, eo);
+					if (to_bnd && lane == 63) bnd[jj] = make_uint2(ho, eo);
+				}
+				hin = (uint32_t)k2a_rot1<64>((int)ho);
+				ein = (uint32_t)k2a_rot1<64>((int)eo);
+			}
+#pragma unroll
+			for (int u = 0; u < 4; ++u) { qc[u] = qn[u]; hb[u] = hn[u]; eb[u] = en[u]; }
+		}
+		L.gen_end();
+	}
+	/* the task's best cell(s): the 64 lane keys reduced once */
+#pragma unroll
+	for (int h = 0; h < (PK ? 2 : 1); ++h) {
+		K2aLLKey k = L.key[h];
+		for (int d = 1; d < 64; d <<= 1) {
+			const int s = __shfl_xor(k.s, d), te = __shfl_xor(k.te, d), qe = __shfl_xor(k.qe, d);
+			const bool take = k2a_ll_better(s, te, qe, k);
+			k.s = take ? s : k.s; k.te = take ? te : k.te; k.qe = take ? qe : k.qe;
+		}
+		if (lane == 0 && (h == 0 || tk.res[1] != tk.res[0])) {
+			K2aLLRes r; r.score = k.s; r.qe = k.qe; r.te = k.te;
+			res[tk.res[h]] = r;
+		}
+	}
+}
+
 extern "C" {
 
 const char *k2a_shim_backend(void) { return "hip:gfx950"; }
@@ -2598,6 +2677,23 @@ int k2a_shim_launch_compact(const K2aPair *pairs, const K2aResult *res, const ui
 {
 	if (n <= 0) return 0;
 	hipLaunchKernelGGL(k2a_compact_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, pairs, res, pos, n, cig, pool);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* local alignment: pk = two alignments per task (packed 16-bit), lds = scores from the LDS table (any m) instead of the register
+ * column profile (m <= 5) */
+int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ll_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (pk) hipLaunchKernelGGL((k2a_ll_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (lds) hipLaunchKernelGGL((k2a_ll_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_ll_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -185,4 +185,21 @@ typedef struct K2aBook {
 } K2aBook;
 
 
+/* local alignment (ksw_ll_qinit / ksw_ll_i16, ksw2amd_ll_batch; ksw2_lane_ll.h).  Rows of a task are the longer of its two sequences,
+ * columns the shorter (swapped = 1: the rows are the query); pk = 1 tasks hold two alignments of the same shape, one per 16-bit half. */
+#define K2A_LL_C    16                 /* rows per lane */
+#define K2A_LL_ROWS (64 * K2A_LL_C)    /* rows per generation: 64 strips */
+typedef struct K2aLL {
+	int32_t m, smax, oe, ge;         /* residue types, largest matrix entry, gap open + extend, gap extend */
+} K2aLL;
+typedef struct K2aLLTask {
+	uint32_t roff[2], coff[2];       /* arena byte offsets of the row / column codes, per half (int32 tasks: [0]) */
+	uint32_t res[2];                 /* result slots of the halves; res[1] == res[0]: one alignment in both halves */
+	int32_t nrows, ncols, swapped, pad;
+	uint64_t boff;                   /* byte offset in the scratch of the generation boundary: 8 bytes per column (tasks over one generation) */
+} K2aLLTask;                         /* 48 bytes */
+typedef struct K2aLLRes {
+	int32_t score, qe, te;           /* ksw2amd_lres_t */
+} K2aLLRes;
+
 #endif
