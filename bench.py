@@ -6,14 +6,17 @@ Headline workload (north_star): 10 000 x 10 000 extensions, band 500, Z-drop 400
 A "step" = ONE call of the drop-in batch entry point (ksw2amd_extz_batch / ksw2amd_extd_batch) on one batch of synthetic
 pairs that sit in ordinary host memory: pack into pinned staging, H2D, fill (+ traceback) kernels, D2H, ksw_extz_t assembly.
 `value` is therefore transfer-inclusive ("wall seconds incl. H2D/D2H"); the library overlaps the phases
-of successive chunks of the batch on its worker threads / streams.  The HBM-resident kernel rate of the same batch
-(ksw2amd_plan_run only, HIP events on the launch stream) is reported next to it as `value_hbm_resident` and prices the
-roofline.  The batch is sized so that the K = 20 steps of the driver's run take a few seconds.
+of successive chunks of the batch on its worker threads / streams.  The batch is sized so that the K = 20 steps of the
+driver's run take a few seconds.
 
-The other configurations of BASELINE.json (config 2, 3, 4 at 4 096 replicas, 5 with channel-derived target lengths) and the
-10 k case with CIGAR / at the n = 1 024 of SURVEY 8d run in the same process and are reported in the `also` array.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  Everything else is
+behind --full, in the same process after the headline's steps: an oracle sample of the timed batch, the same steps through the
+flat-arena entry, the HBM-resident kernel rate of the batch (ksw2amd_plan_run only, HIP events on the launch stream) as
+`value_hbm_resident` with the roofline it prices, the reference on the host cores, and the `also` array: the other configurations
+of BASELINE.json (config 2, 3, 4 at 4 096 replicas, 5 with channel-derived target lengths) and the 10 k case with CIGAR / at
+the n = 1 024 of SURVEY 8d.
 
-Launch:  python bench.py [--gpus 1 --steps K --warmup W]
+Launch:  python bench.py [--gpus 1 --steps K --warmup W] [--full]
          python bench.py --gpus N            (starts its own N ranks through torch.distributed.run)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
@@ -391,7 +394,8 @@ class Job:
             self.ez = None
 
     # ---- HBM-resident: plan_run only, HIP events on the launch stream
-    def resident(self, steps, warmup, stream, min_seconds=0.0):
+    def resident_plan(self):
+        """The plan resident() times (the whole batch, or the slice `resident_n` of it), uploaded but not run; and its batch."""
         wl = self.wl
         nres = wl.get("resident_n")
         if os.environ.get("KSW2_BENCH_ONE_DEVICE") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -402,7 +406,18 @@ class Job:
             S = SCORING
             b = self.lib.make_batch(self.q[:nres], self.t[:nres], self.mat, S["q"], S["e"], S["q2"], S["e2"], w=wl["w"], zdrop=wl["zdrop"], end_bonus=0, flag=wl["flag"])
             b.qlen, b.tlen = self.qlen[:nres], self.tlen[:nres]
-        plan = b.plan() if self.kind in ("exts", "extf") else b.sse_plan(wl["dual"]) if self.sse else b.plan(wl["dual"])
+        return (b.plan() if self.kind in ("exts", "extf") else b.sse_plan(wl["dual"]) if self.sse else b.plan(wl["dual"])), b
+
+    def plan_dtype(self):
+        """dtype_of for the plan resident() would time, without running it (what a run without --full reports as `dtype`)."""
+        plan, b = self.resident_plan()
+        try:
+            return dtype_of(self, dict(n=b.n, packed_pairs=plan.packed_pairs()))
+        finally:
+            plan.close()
+
+    def resident(self, steps, warmup, stream, min_seconds=0.0):
+        plan, b = self.resident_plan()
         cells = plan.cells()
         for _ in range(warmup):
             plan.run(stream)
@@ -647,7 +662,8 @@ def compact_line(out, detail_path):
         line["config"]["rank0_scatter_gather"] = {k: sg[k] for k in ("value", "pairs_per_step", "ms_per_step", "records_checked")}
     if "cfg5_lpt_imbalance" in cfg and "max_over_mean_cells" in cfg["cfg5_lpt_imbalance"]:
         line["config"]["cfg5_lpt_max_over_mean"] = cfg["cfg5_lpt_imbalance"]["max_over_mean_cells"]
-    line["roofline"] = {k: out["roofline"][k] for k in ROOFLINE_LINE_KEYS if k in out["roofline"]}
+    if "roofline" in out:                                    # --full
+        line["roofline"] = {k: out["roofline"][k] for k in ROOFLINE_LINE_KEYS if k in out["roofline"]}
     if "cpu_baseline" in out:
         cb = out["cpu_baseline"]
         line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample", "pairs_per_s", "all_cores") if k in cb}
@@ -729,11 +745,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="10k", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs", type=int, default=0, help="override pairs per step and GPU (parity/debug only)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--also-cpu-seconds", type=float, default=3.0, help="CPU sample per `also` workload (1 thread, then all cores); 0 = none")
-    ap.add_argument("--also", default=None, help="comma-separated workloads for the `also` array ('' = none; default: the other configs at N = 1)")
-    ap.add_argument("--no-also", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: oracle samples, the flat-arena entry, the HBM-resident loop and roofline, the reference "
+                         "on the host cores, the `also` workloads, with N > 1 the rank-0 scatter / gather leg and the config-5 partition.  Without it "
+                         "a run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU sample of the headline (1 thread, then all cores)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU samples")
+    ap.add_argument("--also-cpu-seconds", type=float, default=3.0, help="--full: CPU sample per `also` workload (1 thread, then all cores); 0 = none")
+    ap.add_argument("--also", default=None, help="--full: comma-separated workloads for the `also` array ('' = none; default: the other configs at N = 1)")
+    ap.add_argument("--no-also", action="store_true", help="--full: no `also` array")
     ap.add_argument("--resident-only", action="store_true", help="profiling: only the HBM-resident kernel loop (what rocprofv3 should see)")
     ap.add_argument("--approx", action="store_true", help="OR KSW_EZ_APPROX_MAX into the flags (score + corner CIGAR only, as in the reference)")
     ap.add_argument("--sse-compat", action="store_true", help="OR KSW2AMD_EZ_SSE_COMPAT into the flags: the SSE kernels' own results through the SSE-compatible kernels")
@@ -744,6 +764,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.resident_only:
         ap.error("--dump-outputs needs the timed batch entry point; --resident-only skips it")
+    if args.also and not args.full:
+        ap.error("--also names workloads of --full")
 
     # N > 1 without a launcher: start our own ranks BEFORE anything touches a GPU (a process that has initialised HIP is never
     # re-exec'ed); the child ranks print the JSON line, we pass their exit code on
@@ -850,11 +872,12 @@ def main():
         pairs_all = job.n * world
     else:
         cells_all, pairs_all = float(job.cells), job.n
-    parity = job.parity_sample(16) if rank == 0 else None      # outside the timed region: the results the timed calls returned
+    # --full only from here to the `also` loop: everything the headline's line does not need
+    parity = job.parity_sample(16) if rank == 0 and args.full else None      # outside the timed region: the results the timed calls returned
     # the same K steps through the flat entry point (one arena + offsets, page-locked once): what a caller that owns its read
     # buffer would use.  Timed exactly like the loop above.
     dt_flat, parity_flat = None, None
-    if job.flat_ready():
+    if args.full and job.flat_ready():
         for _ in range(max(1, min(args.warmup, 2))):
             job.e2e_step(flat=True)
         barrier()
@@ -874,45 +897,49 @@ def main():
     barrier()
     # north_star's form of the multi-GPU path, next to the host-side sharding above ("report both"): rank 0 holds
     # the whole batch, LPT-partitions it, scatters sequences + parameters and gathers records + CIGARs over RCCL
-    sg = scatter_gather_leg(lib, job, rank, world, barrier, red_dev) if world > 1 and job.kind in ("extz", "extd") else None
-    res = job.resident(args.steps, max(1, min(args.warmup, 3)), stream)
+    sg = scatter_gather_leg(lib, job, rank, world, barrier, red_dev) if args.full and world > 1 and job.kind in ("extz", "extd") else None
+    res = job.resident(args.steps, max(1, min(args.warmup, 3)), stream) if args.full else None
     lib.release_cache()
 
     out = None
     if rank == 0:
-        rl = roofline_of(job, res, args.workload)
-        rl["note"] = ("integer-VALU bound (no dense contraction, SURVEY 8d); peak = the guide's vector peak 256CU x 4SIMD x 32 lanes x 2.4GHz x 2 "
-                      "(packed int16); measured with tools/probe/valu_rate.hip (profiles/r1d_valu_rate.txt): v_pk_*_i16, v_max_i32, v_bfi issue one "
-                      "wave64 instruction per 4 cycles per SIMD (add/sub/xor/bitop3: 2), i.e. 39.3 T lane-instr/s = 78.6 T 16-bit ops/s, half of `peak`")
         value = cells_all * args.steps / dt / 1e9
         out = {
             "metric": "GCUPS (DP cells/s) + pairs/s at fixed (qlen,tlen,band)",
             "value": round(value, 3), "unit": "GCUPS",
             "value_definition": "exact-band cells of all pairs / wall time of `steps` calls of the batch entry point on host-memory inputs: "
                                 "pack + H2D + kernels + D2H + ksw_extz_t assembly (SURVEY 8d)",
-            "value_hbm_resident": rl["kernel_gcups"],
-            "value_flat_arena": round(cells_all * args.steps / dt_flat / 1e9, 3) if dt_flat else None,
-            "value_flat_arena_definition": "the same steps through ksw2amd_ext?_batch_flat: the batch as one page-locked host arena + offsets (no per-pair gather, "
-                                           "no host pass over the bytes); transfer-inclusive like `value`" if dt_flat else None,
             "pairs_per_s": round(pairs_all * args.steps / dt, 1),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "timed_region_s": round(dt, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype_of(job, res),
+            # the kernels' number format: of the resident plan when it ran (--full), else of the same plan uploaded and not run
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype_of(job, res) if res is not None else job.plan_dtype(),
             "data": "synthetic" if not plumbing else "synthetic -- PLUMBING TEST ON THE CPU SIMULATOR, NOT A MEASUREMENT",
             "config": {"workload": describe(job, world), "cells_per_step_per_gpu": job.cells,
                        "setup_priming_batches": priming,      # untimed library set-up batches in front of the W warm-up steps (0 when W >= 3)
                        "host_pipeline": {k: stats1[k] - stats0[k] for k in stats1},
                        "parallelism": "pairs sharded over %d GPU(s), one process per GPU, no collective in the data path" % world},
-            "roofline": rl,
-            "parity_sample": parity["result"], "parity_detail": parity,
         }
-        if dt_flat:
-            out["parity_sample_flat_arena"] = parity_flat["result"]
-        if sg:
-            out["config"]["rank0_scatter_gather"] = sg
         if per_rank:
             out["config"]["per_rank"] = per_rank
         else:
             out["config"]["host_thread_ms_per_step"] = host_ms
+    if rank == 0 and args.full:
+        rl = roofline_of(job, res, args.workload)
+        rl["note"] = ("integer-VALU bound (no dense contraction, SURVEY 8d); peak = the guide's vector peak 256CU x 4SIMD x 32 lanes x 2.4GHz x 2 "
+                      "(packed int16); measured with tools/probe/valu_rate.hip (profiles/r1d_valu_rate.txt): v_pk_*_i16, v_max_i32, v_bfi issue one "
+                      "wave64 instruction per 4 cycles per SIMD (add/sub/xor/bitop3: 2), i.e. 39.3 T lane-instr/s = 78.6 T 16-bit ops/s, half of `peak`")
+        out.update({
+            "value_hbm_resident": rl["kernel_gcups"],
+            "value_flat_arena": round(cells_all * args.steps / dt_flat / 1e9, 3) if dt_flat else None,
+            "value_flat_arena_definition": "the same steps through ksw2amd_ext?_batch_flat: the batch as one page-locked host arena + offsets (no per-pair gather, "
+                                           "no host pass over the bytes); transfer-inclusive like `value`" if dt_flat else None,
+            "roofline": rl,
+            "parity_sample": parity["result"], "parity_detail": parity,
+        })
+        if dt_flat:
+            out["parity_sample_flat_arena"] = parity_flat["result"]
+        if sg:
+            out["config"]["rank0_scatter_gather"] = sg
         if world > 1 and not plumbing:
             try:
                 out["config"]["cfg5_lpt_imbalance"] = lpt_imbalance(world)
@@ -932,6 +959,8 @@ def main():
         names = [] if args.also is None else names
     if world > 1 and args.also is None and not (args.no_also or args.pairs or args.approx or args.sse_compat or args.workload != "10k"):
         names = list(ALSO_MULTI)                                 # the multi-GPU configurations at their per-GPU share, every rank its own slice
+    if not args.full:
+        names = []
     also = []
     mismatch = parity is not None and parity["result"] == "MISMATCH"
     if dt_flat and rank == 0 and parity_flat is not None and parity_flat["result"] == "MISMATCH":

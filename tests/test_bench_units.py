@@ -72,7 +72,8 @@ def test_bench_two_ranks_plumbing(sim, tmp_path):
     """`python bench.py --gpus 2` end to end on the CPU tier: the script launches its own two ranks through torch.distributed.run
     (before anything could touch a GPU), they rendezvous over gloo, time K steps between barriers, reduce MAX time / SUM cells,
     run the rank-0 scatter/gather leg (ksw2_amd/parallel.py) and rank 0 prints ONE well-formed JSON line.  The simulator build stands
-    in for the per-rank GPU (KSW2_BENCH_PLUMBING_LIB): the line says that it is not a measurement."""
+    in for the per-rank GPU (KSW2_BENCH_PLUMBING_LIB): the line says that it is not a measurement.  --full: the oracle sample, the
+    scatter/gather leg and the roofline are not part of a plain run."""
     import json
     import sys
     root = os.path.dirname(SIM_DIR.rstrip("/")).rsplit("/tests", 1)[0]
@@ -80,7 +81,7 @@ def test_bench_two_ranks_plumbing(sim, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg3", "--pairs", "24",
-                        "--no-cpu", "--no-also"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu", "--no-also"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -142,6 +143,38 @@ def test_bench_dump_outputs_repeat(sim, tmp_path):
         a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
         assert a.dtype == np.float64 and np.array_equal(a, b), f
     assert len(np.load(str(tmp_path / "a" / "score.npy"))) == 12
+
+
+def test_bench_plain_run_is_the_headline_only(sim, tmp_path):
+    """Without --full a run times the headline and prints its line, nothing else: no oracle sample, no flat-arena entry, no resident loop or
+    roofline, no CPU sample, no `also` array.  What it shares with a --full run of the same arguments says the same (metric, unit, direction,
+    dtype: the plain run reads the number format off the resident plan, uploaded and not run), and the timed steps return the same outputs."""
+    import json
+    import sys
+    root = os.path.dirname(SIM_DIR.rstrip("/")).rsplit("/tests", 1)[0]
+    env = dict(os.environ, KSW2_BENCH_PLUMBING_LIB=os.path.join(SIM_DIR, "libksw2_amd_sim.so"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg3", "--pairs", "12"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / mode)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (mode, r.stdout[-2000:], r.stderr[-3000:])
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    assert not {"roofline", "value_hbm_resident", "value_flat_arena", "parity_sample", "parity_sample_flat_arena", "cpu_baseline", "also"} & set(plain), plain
+    assert {"roofline", "value_hbm_resident", "value_flat_arena", "parity_sample"} <= set(full) and full["parity_sample"] == "ok"
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["workload"] == full["config"]["workload"]
+    names = sorted(os.listdir(str(tmp_path / "plain")))
+    assert names == sorted(os.listdir(str(tmp_path / "full"))) and "score.npy" in names
+    assert all(np.array_equal(np.load(str(tmp_path / "plain" / f)), np.load(str(tmp_path / "full" / f))) for f in names)
+    # the options of --full name work a plain run does not do
+    r = subprocess.run(cmd + ["--also", "cfg2"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "--full" in r.stderr
 
 
 def test_recorded_traffic_names_the_latest_profile_of_the_same_workload():

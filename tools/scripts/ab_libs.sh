@@ -8,7 +8,7 @@ for rep in $(seq 1 $REPS); do
 for w in $WLS; do
 for v in $VARS; do
 	[ -f build_ab/lib_$v.so ] || { echo "build_ab/lib_$v.so is missing" >&2; exit 1; }
-	KSW2AMD_LIB=$PWD/build_ab/lib_$v.so timeout 600 python bench.py --workload $w --steps 6 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('rep$rep %-10s %-10s value %8.1f resident %8.1f kernel_ms %9.4f parity %s' % ('$v', '$w', d['value'], d['value_hbm_resident'], d['roofline']['kernel_ms'], d['parity_sample']))" >> $O
+	KSW2AMD_LIB=$PWD/build_ab/lib_$v.so timeout 600 python bench.py --full --workload $w --steps 6 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('rep$rep %-10s %-10s value %8.1f resident %8.1f kernel_ms %9.4f parity %s' % ('$v', '$w', d['value'], d['value_hbm_resident'], d['roofline']['kernel_ms'], d['parity_sample']))" >> $O
 done
 done
 done

@@ -3,7 +3,7 @@
 # same box back to back.  usage: tools/scripts/e2e_threads_ab.sh  > gpurun_out/<tag>/e2e_threads_ab.txt
 run() { # label, workload, env...
 	local label=$1 wl=$2; shift 2
-	env "$@" python bench.py --workload $wl --steps 12 --warmup 4 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-28s %-6s value %8.1f  flat %8.1f  resident %8.1f  ms/step %7.3f' % ('$label', '$wl', d['value'], d['value_flat_arena'] or 0, d['value_hbm_resident'], d['ms_per_step']))"
+	env "$@" python bench.py --full --workload $wl --steps 12 --warmup 4 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-28s %-6s value %8.1f  flat %8.1f  resident %8.1f  ms/step %7.3f' % ('$label', '$wl', d['value'], d['value_flat_arena'] or 0, d['value_hbm_resident'], d['ms_per_step']))"
 }
 for rep in 1 2; do
 	for t in 6 8 12 16; do run "threads=$t" cfg2 KSW2AMD_THREADS=$t; done

@@ -3,8 +3,8 @@
 # KSW2_BENCH_ONE_DEVICE=1 hooks), against one rank with the whole batch.  usage: rehearsal_8rank.sh [out.json]
 OUT=${1:-gpurun_out/rehearsal_8rank.json}
 export KSW2_BENCH_BACKEND=gloo KSW2_BENCH_ONE_DEVICE=1 KSW2AMD_MAX_BYTES=$((28*1024*1024*1024))
-run1() { python3 bench.py --workload $1 --steps $2 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1; }
-runN() { python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29633 bench.py --gpus 8 --workload $1 --pairs $3 --steps $2 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1; }
+run1() { python3 bench.py --full --workload $1 --steps $2 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1; }
+runN() { python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29633 bench.py --gpus 8 --full --workload $1 --pairs $3 --steps $2 --warmup 2 --no-cpu --no-also 2>/dev/null | tail -1; }
 {
 echo '{"what": "N gloo ranks sharing ONE MI355X and one host against one rank with the whole batch (tools/scripts/rehearsal_8rank.sh): value = all ranks cells over the slowest rank time", "runs": ['
 echo '{"name": "one_rank_10k", "line": '; run1 10k 5; echo '},'

@@ -2,7 +2,7 @@
 # GPU box: uniform plans on / off (KSW2AMD_UNIFORM), end to end, same box back to back: config 2 and the 10 k headline.
 one() { # label workload steps env...
 	local label=$1 wl=$2 st=$3; shift 3
-	env "$@" python bench.py --workload $wl --steps $st --warmup 5 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-12s %-5s value %8.1f  flat %8.1f  resident %8.1f  ms/step %8.3f  parity %s' % ('$label', '$wl', d['value'], d['value_flat_arena'] or 0, d['value_hbm_resident'], d['ms_per_step'], d['parity_sample']))"
+	env "$@" python bench.py --full --workload $wl --steps $st --warmup 5 --no-cpu --no-also 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-12s %-5s value %8.1f  flat %8.1f  resident %8.1f  ms/step %8.3f  parity %s' % ('$label', '$wl', d['value'], d['value_flat_arena'] or 0, d['value_hbm_resident'], d['ms_per_step'], d['parity_sample']))"
 }
 for rep in 1 2 3; do one uniform=1 cfg2 20 KSW2AMD_UNIFORM=1; one uniform=0 cfg2 20 KSW2AMD_UNIFORM=0; done
 for rep in 1 2; do one uniform=1 10k 10 KSW2AMD_UNIFORM=1; one uniform=0 10k 10 KSW2AMD_UNIFORM=0; done
