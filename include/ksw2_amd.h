@@ -287,6 +287,32 @@ typedef struct {
 } ksw2amd_lres_t;
 int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 
+/* Local alignment with start cell and CIGAR (new; what a caller of ksw_ll_i16 does next by hand -- reverse both prefixes, a second
+ * pass for the start, a global alignment of the interval -- as one call).  For every pair:
+ *   score, qe, te   exactly what ksw2amd_ll_batch returns;
+ *   qb, tb          with (s', qe', te') = ksw2amd_ll_batch's result on reverse(query[0..qe]), reverse(target[0..te]): qb = qe - qe',
+ *                   tb = te - te' (s' == score always).  In words: among the start cells of the best-scoring alignments that end in
+ *                   (qe, te), the largest tb, then the largest qb.  The alignment covers query[qb..qe] and target[tb..te], inclusive;
+ *   cigar           exactly the CIGAR of the scalar ksw_extz(km, qe-qb+1, query+qb, te-tb+1, target+tb, m, mat, gapo, gape, -1, -1,
+ *                   KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)), &ez), whose global score equals `score` (checked
+ *                   for every pair; a mismatch is reported as an error, never returned).  With gapo + gape > 0 it begins and ends with M.
+ * flag: KSW_EZ_SCORE_ONLY (coordinates only, n_cigar = 0, no third stage), KSW_EZ_RIGHT, KSW_EZ_REV_CIGAR; any other bit is
+ * KSW2AMD_E_PARAM.  A best score of 0 (an empty sequence, a matrix without a positive entry): score = 0, qb = qe = tb = te = -1,
+ * n_cigar = 0, nothing launched for the pair.  Arguments as for ksw2amd_ll_batch (m 1..127, gapo / gape 0..127, every residue code
+ * < m), all checked before anything is staged or launched.  The start-cell pass runs on the device from what the forward pass left
+ * there (no download, host reversal or second upload in between).  aln[] is zero-initialised by the caller or holds reusable CIGAR
+ * buffers (cigar / m_cigar, grown through km like ksw_extz_t.cigar).  Device failures: a negative code, no CPU fallback. */
+typedef struct {
+	int32_t score;              /* as ksw2amd_ll_batch */
+	int32_t qb, qe, tb, te;     /* 0-based, inclusive */
+	int32_t m_cigar, n_cigar;
+	uint32_t *cigar;            /* len<<4 | op */
+} ksw2amd_laln_t;
+int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+/* one pair, on a profile from ksw_ll_qinit; returns the score.  On a device failure or a bad argument it returns 0 with the four
+ * coordinates -1 and n_cigar = 0, and reports like ksw_ll_i16 */
+int ksw2amd_ll_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln);
+
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t
  * or NULL), fetch = wait + download + fill ez[]. */

@@ -60,6 +60,12 @@ class LocalResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("qe", ctypes.c_int32), ("te", ctypes.c_int32)]
 
 
+class LocalAln(ctypes.Structure):
+    """ksw2amd_laln_t: score, the alignment's first and last cell, CIGAR (ksw2amd_ll_align_batch)."""
+    _fields_ = [("score", ctypes.c_int32), ("qb", ctypes.c_int32), ("qe", ctypes.c_int32), ("tb", ctypes.c_int32), ("te", ctypes.c_int32),
+                ("m_cigar", ctypes.c_int32), ("n_cigar", ctypes.c_int32), ("cigar", ctypes.POINTER(ctypes.c_uint32))]
+
+
 class Pair(ctypes.Structure):
     _fields_ = [("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("tlen", ctypes.c_int32),
                 ("w", ctypes.c_int32), ("zdrop", ctypes.c_int32), ("end_bonus", ctypes.c_int32), ("flag", ctypes.c_int32)]
@@ -92,7 +98,7 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat", "ksw2amd_host_register", "ksw2amd_host_unregister",
            "ksw2amd_device_alloc", "ksw2amd_device_free", "ksw2amd_device_upload", "ksw2amd_device_download", "ksw2amd_rerun_count",
            "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device",
-           "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch"]
+           "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -100,7 +106,7 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_extz_batch", "ksw2amd_extd_batch", "ksw2amd_exts_batch", "ksw2amd_extf_batch", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device", "ksw2amd_plan_create",
                 "ksw2amd_sse_plan_create", "ksw2amd_exts_plan_create", "ksw2amd_extf_plan_create", "ksw2amd_plan_run",
                 "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
-                "ksw_ll_i16", "ksw2amd_ll_batch"]
+                "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -230,6 +236,9 @@ class Library:
             L.ksw_ll_qinit.restype = ctypes.c_void_p
             L.ksw_ll_i16.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
             L.ksw2amd_ll_batch.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+        if hasattr(L, "ksw2amd_ll_align_batch"):    # (nor have the simulator builds of tests/ll_util.py the start-cell pass)
+            L.ksw2amd_ll_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ll_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -392,6 +401,52 @@ class Library:
         finally:
             _libc.free(prof)
         return int(score), qe.value, te.value
+
+    @staticmethod
+    def _aln_to_dict(a, free_cigar=True):
+        d = dict(score=int(a.score), qb=int(a.qb), qe=int(a.qe), tb=int(a.tb), te=int(a.te), n_cigar=int(a.n_cigar),
+                 cigar=[int(a.cigar[k]) for k in range(a.n_cigar)])
+        if free_cigar and a.cigar:
+            _libc.free(ctypes.cast(a.cigar, ctypes.c_void_p))
+        return d
+
+    def ll_align_batch(self, queries, targets, mat, gapo, gape, flag=0, m=None):
+        """ksw2amd_ll_align_batch(km=NULL, ...): local alignment with start cell and CIGAR -> list of dicts score, qb, qe, tb, te,
+        n_cigar, cigar (query[qb..qe] against target[tb..te], inclusive; flag: KSW_EZ_SCORE_ONLY / KSW_EZ_RIGHT / KSW_EZ_REV_CIGAR)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        n = len(queries)
+        if len(targets) != n:
+            raise ValueError("queries and targets differ in length")
+        keep = [np.ascontiguousarray(x, dtype=np.uint8) for x in list(queries) + list(targets)]
+        pairs = (LocalPair * max(n, 1))()
+        for i in range(n):
+            qa, ta = keep[i], keep[n + i]
+            pairs[i].query, pairs[i].target = qa.ctypes.data, ta.ctypes.data
+            pairs[i].qlen, pairs[i].tlen = len(qa), len(ta)
+        aln = (LocalAln * max(n, 1))()
+        rc = self.lib.ksw2amd_ll_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, flag, n, pairs, aln)
+        out = [self._aln_to_dict(aln[i]) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def ll_align(self, query, target, mat, gapo, gape, flag=0, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_ll_align(km=NULL, ...) -> dict like ll_align_batch's."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        qa, qp = self._seq(query)
+        ta, tp = self._seq(target)
+        prof = self.lib.ksw_ll_qinit(None, size, len(qa), qp, m, mat.ctypes.data_as(_i8p))
+        if not prof:
+            raise Ksw2Error("ksw_ll_qinit: " + self.last_error())
+        try:
+            a = LocalAln()
+            score = self.lib.ksw2amd_ll_align(None, prof, len(ta), tp, gapo, gape, flag, ctypes.byref(a))
+        finally:
+            _libc.free(prof)
+        d = self._aln_to_dict(a)
+        assert d["score"] == int(score)
+        return d
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

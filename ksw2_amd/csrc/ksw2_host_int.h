@@ -286,5 +286,15 @@ size_t thread_cached_device_bytes(void);
 void *shared_upload_stream(void);
 int exts_chunk(void *ctx_, int beg, int end, int share, pend_t *pd);
 int extf_chunk(void *ctx_, int beg, int end, int share, pend_t *pd);
+int ext_batch_scalar(int dual, void *km, const ksw2amd_scoring_t *sc, int n, const ksw2amd_pair_t *pairs, ksw_extz_t *ez);      /* the batch path behind ksw2amd_extz_batch under the scalar ksw_extz / ksw_extd contract */
+/* local alignment (ksw2_host_ll.c).  ll_rev_fn = k2a_shim_launch_ll_rev, passed in by ksw2_host_lla.c: ksw2_host_ll.o must not name it */
+typedef int (*ll_rev_fn)(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                         uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+typedef struct {
+	int32_t size, qlen, m, pad;      /* ksw_ll_qinit's block: then qlen query codes, then m * m matrix entries */
+} ll_prof_t;
+int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
+int ll_bad_code(const uint8_t *s, int len, int m);
+int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs);
 #pragma GCC visibility pop
 #endif

@@ -7,6 +7,8 @@
  * the task table and the pen tables, one upload, one launch per kernel form, one 12-byte-per-pair download.  Kernels: ksw2_lane_ll.h.
  *
  * This is the only host object that calls k2a_shim_launch_ll (tests/sim links the other four against a simulator without it).
+ * ksw2amd_ll_align_batch (ksw2_host_lla.c) runs its start-cell pass from what a chunk staged here: it hands ll_batch_ex the launch as a
+ * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
  */
 #include "ksw2_host_int.h"
 
@@ -35,7 +37,7 @@ static int cmp_cost(const void *a_, const void *b_)
 	return a->idx < b->idx ? -1 : a->idx > b->idx;
 }
 
-static int ll_check_args(int m, const int8_t *mat, int gapo, int gape)
+int ll_check_args(int m, const int8_t *mat, int gapo, int gape)
 {
 	if (m < 1 || m > K2A_MAXM) return fail(KSW2AMD_E_PARAM, "local alignment: m must be 1..127%s", "");
 	if (!mat) return fail(KSW2AMD_E_PARAM, "local alignment: mat is NULL%s", "");
@@ -43,15 +45,17 @@ static int ll_check_args(int m, const int8_t *mat, int gapo, int gape)
 	return KSW2AMD_OK;
 }
 
-static int ll_bad_code(const uint8_t *s, int len, int m)
+int ll_bad_code(const uint8_t *s, int len, int m)
 {
 	int i;
 	for (i = 0; i < len; ++i) if (s[i] >= m) return 1;
 	return 0;
 }
 
-/* one chunk: pairs [0, n) of the caller's, all validated */
-static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
+/* one chunk: pairs [0, n) of the caller's, all validated.  rev: the start-cell pass (beg[i] = its score, qb, tb), launched behind the
+ * forward pass on the same task table, tables, sequences and results in device memory; one download brings back both arrays */
+static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res,
+                    ll_rev_fn rev, K2aLLBeg *beg)
 {
 	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
@@ -60,6 +64,7 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 	K2aLLTask *tk = 0;
 	uint8_t *h_arena = 0, *d_arena = 0, *d_scr = 0;
 	K2aLLRes *h_res = 0, *d_res = 0;
+	const size_t res_bytes = (sizeof(K2aLLRes) + (rev ? sizeof(K2aLLBeg) : 0)) * (size_t)n;      /* K2aLLRes[n], then K2aLLBeg[n] */
 	size_t cap_h = 0, cap_d = 0, cap_s = 0, cap_hr = 0, cap_dr = 0;
 	int npk = 0, ni32 = 0, ntk_pk = 0, ntk = 0, i, rc = KSW2AMD_OK;
 	size_t tab_off, seq_off, bytes, scr = 0;
@@ -69,6 +74,7 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 		const ksw2amd_lpair_t *p = &pairs[i];
 		ll_sort_t s;
 		res[i].score = 0; res[i].qe = res[i].te = -1;
+		if (rev) { beg[i].score = 0; beg[i].qb = beg[i].tb = -1; }
 		if (p->qlen <= 0 || p->tlen <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
 		s.rows = imax(p->qlen, p->tlen); s.cols = imin(p->qlen, p->tlen); s.sw = p->qlen > p->tlen; s.idx = (uint32_t)i;
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
@@ -93,6 +99,7 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 	qsort(i32, (size_t)ni32, sizeof(ll_sort_t), cmp_cost);
 	ntk = ntk_pk + ni32;
 	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers");
+	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] ll-rev: pk_tasks=%d int32_tasks=%d profile=%s\n", ntk_pk, ni32, lds ? "lds" : "registers");
 	if (ntk == 0) { free(pk); free(i32); return KSW2AMD_OK; }
 	/* arena: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once) */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
@@ -102,8 +109,8 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 	for (i = 0; i < ni32; ++i) bytes += align_up((size_t)i32[i].rows, 4) + align_up((size_t)i32[i].cols, 4);
 	h_arena = (uint8_t*)cache_get(BUF_HSEQ, bytes, &cap_h);
 	d_arena = (uint8_t*)cache_get(BUF_SEQ, bytes, &cap_d);
-	h_res = (K2aLLRes*)cache_get(BUF_HRES, sizeof(K2aLLRes) * (size_t)n, &cap_hr);
-	d_res = (K2aLLRes*)cache_get(BUF_RES, sizeof(K2aLLRes) * (size_t)n, &cap_dr);
+	h_res = (K2aLLRes*)cache_get(BUF_HRES, res_bytes, &cap_hr);
+	d_res = (K2aLLRes*)cache_get(BUF_RES, res_bytes, &cap_dr);
 	if (!h_arena || !d_arena || !h_res || !d_res) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: buffer allocation failed: %s", k2a_shim_last_error()); goto out; }
 	tk = (K2aLLTask*)h_arena;
 	{
@@ -145,11 +152,18 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 		if (k2a_shim_h2d(d_arena, h_arena, bytes, st)
 		    || k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_arena, d_arena + tab_off, d_scr, d_res, st)
 		    || k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_arena, d_arena + tab_off, d_scr, d_res, st)
-		    || k2a_shim_d2h(h_res, d_res, sizeof(K2aLLRes) * (size_t)n, st)
+		    || (rev && rev(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_arena, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
+		    || (rev && rev(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_arena, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
+		    || k2a_shim_d2h(h_res, d_res, res_bytes, st)
 		    || k2a_shim_stream_sync(st)) { rc = fail(KSW2AMD_E_NODEVICE, "local alignment: %s", k2a_shim_last_error()); goto out; }
 	}
 	for (i = 0; i < npk; ++i) { const K2aLLRes *r = &h_res[pk[i].idx]; res[pk[i].idx].score = r->score; res[pk[i].idx].qe = r->qe; res[pk[i].idx].te = r->te; }
 	for (i = 0; i < ni32; ++i) { const K2aLLRes *r = &h_res[i32[i].idx]; res[i32[i].idx].score = r->score; res[i32[i].idx].qe = r->qe; res[i32[i].idx].te = r->te; }
+	if (rev) {
+		const K2aLLBeg *hb = (const K2aLLBeg*)(h_res + n);
+		for (i = 0; i < npk; ++i) beg[pk[i].idx] = hb[pk[i].idx];
+		for (i = 0; i < ni32; ++i) beg[i32[i].idx] = hb[i32[i].idx];
+	}
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (h_arena) cache_put(BUF_HSEQ, h_arena, cap_h);
@@ -160,11 +174,12 @@ out:
 	return rc;
 }
 
-int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
+/* ksw2amd_ll_batch (rev = 0), and the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c) */
+int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs)
 {
 	int i, rc, beg = 0, smax = -128;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
-	if (n < 0 || (n > 0 && (!pairs || !res))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
 	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */
 		const ksw2amd_lpair_t *p = &pairs[i];
 		char msg[96];
@@ -182,22 +197,23 @@ int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const 
 		int end;
 		for (end = beg; end < n; ++end) {
 			const size_t rows = (size_t)imax(imax(pairs[end].qlen, pairs[end].tlen), 0), cols = (size_t)imax(imin(pairs[end].qlen, pairs[end].tlen), 0);
-			const size_t pb = rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0);
+			const size_t pb = rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0);
 			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
 			b += pb;
 		}
-		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, pairs + beg, res + beg);
+		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, pairs + beg, res + beg, rev, rev ? begs + beg : 0);
 		if (rc) return rc;
 		beg = end;
 	}
 	return KSW2AMD_OK;
 }
 
-/* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */
-typedef struct {
-	int32_t size, qlen, m, pad;      /* then qlen query codes, then m * m matrix entries */
-} ll_prof_t;
+int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
+{
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0);
+}
 
+/* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */
 void *ksw_ll_qinit(void *km, int size, int qlen, const uint8_t *query, int m, const int8_t *mat)
 {
 	const int ql = imax(qlen, 0);

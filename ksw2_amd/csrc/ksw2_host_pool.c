@@ -909,6 +909,12 @@ static int route_batch(int dual, void *km, const ksw2amd_scoring_t *sc, int n, c
 	return rc;
 }
 
+/* the same machinery under the scalar contract (no early rejects of the "...2_sse" signatures): the CIGAR stage of ksw2amd_ll_align_batch */
+int ext_batch_scalar(int dual, void *km, const ksw2amd_scoring_t *sc, int n, const ksw2amd_pair_t *pairs, ksw_extz_t *ez)
+{
+	return run_batch(dual, 1, km, sc, n, pairs, ez, 0);
+}
+
 int ksw2amd_extz_batch(void *km, const ksw2amd_scoring_t *sc, int n, const ksw2amd_pair_t *pairs, ksw_extz_t *ez)
 {
 	return route_batch(0, km, sc, n, pairs, ez);

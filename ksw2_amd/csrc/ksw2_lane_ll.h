@@ -81,8 +81,13 @@ K2A_FN bool k2a_ll_better(int s, int te, int qe, const K2aLLKey &k)
 }
 K2A_FN void k2a_ll_key_reset(K2aLLKey &k) { k.s = 0; k.te = -1; k.qe = -1; }
 
-/* PK: two alignments per lane (packed form); LDSP: scores from the LDS table (else the register column profile, m <= 5) */
-template<bool PK, bool LDSP>
+/* PK: two alignments per lane (packed form); LDSP: scores from the LDS table (else the register column profile, m <= 5).
+ * REV: the start-cell pass of ksw2amd_ll_align_batch -- the same recurrence over the REVERSED prefixes that
+ * end in the forward pass's best cell: half h covers rows [0, rl[h]) and columns [0, cl[h]) of the task (set_limits), row i holds
+ * r[rl - 1 - i] and column j holds c[cl - 1 - j].  The two halves of a packed task run over their bounding rectangle; a cell depends
+ * only on cells above and to its left, so the cells outside a half's own rectangle cannot change one inside it and only have to be
+ * kept out of that half's maximum: the row-maximum update carries a per-half column test, gen_end a per-half row test. */
+template<bool PK, bool LDSP, bool REV = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
 	int nrows, ncols, swapped, m, lane, i0;
@@ -92,6 +97,17 @@ struct K2aLaneLL {
 	uint32_t pa[C], pb[PK ? C : 1], pw[LDSP ? 1 : C];   /* register profile: pen bytes for column codes 0..3 (pa: low half, pb: high
 	                                                     * half), pw: code 4; LDS profile: pa / pb = row code * m */
 	K2aLLKey key[NH];
+	int rl[REV ? NH : 1], cl[REV ? NH : 1];    /* REV: rows / columns of each half's prefix rectangle (0: the half scored 0) */
+
+	/* REV, after init: the halves' limits; the task then runs over rows [0, max rl) and columns [0, max cl) */
+	K2A_FN void set_limits(const int *rl_, const int *cl_)
+	{
+		nrows = ncols = 0;
+		for (int h = 0; h < (REV ? NH : 1); ++h) {
+			rl[h] = rl_[h]; cl[h] = cl_[h];
+			nrows = k2a_max(nrows, rl[h]); ncols = k2a_max(ncols, cl[h]);
+		}
+	}
 
 	K2A_FN void init(const K2aLL &par, const K2aLLTask &tk, int lane_)
 	{
@@ -109,7 +125,13 @@ struct K2aLaneLL {
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			const int i = i0 + c;
-			const uint32_t a = i < nrows ? r0[i] : 0u, b = (PK && i < nrows) ? r1[i] : 0u;
+			uint32_t a, b;
+			if (REV) {                             /* row i of a half is r[rl - 1 - i]; past the half's limit: code 0, never a byte out of bounds */
+				a = i < rl[0] ? r0[rl[0] - 1 - i] : 0u;
+				b = (PK && i < rl[REV ? NH - 1 : 0]) ? r1[rl[REV ? NH - 1 : 0] - 1 - i] : 0u;
+			} else {
+				a = i < nrows ? r0[i] : 0u; b = (PK && i < nrows) ? r1[i] : 0u;
+			}
 			hl[c] = 0; f[c] = 0; rmax[c] = 0; rcol[c] = 0;
 			if (LDSP) {
 				pa[c] = a * (uint32_t)m;
@@ -142,6 +164,8 @@ struct K2aLaneLL {
 			} else sel = q0 | 0x0c0c0c00u;
 		}
 		const uint32_t jj2 = PK ? (uint32_t)jj * 0x10001u : (uint32_t)jj;
+		/* REV, packed: all ones in a half whose own rectangle holds column jj (the int32 form runs its exact rectangle) */
+		const uint32_t cmask = (REV && PK) ? (jj < cl[0] ? 0xffffu : 0u) | (jj < cl[REV ? NH - 1 : 0] ? 0xffff0000u : 0u) : 0xffffffffu;
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			uint32_t pen;
@@ -154,9 +178,10 @@ struct K2aLaneLL {
 				const uint32_t hoe = k2a_ll_subs(h, oe);
 				e = k2a_ll_max(hoe, k2a_ll_subs(e, ge));
 				f[c] = k2a_ll_max(hoe, k2a_ll_subs(f[c], ge));
-				const uint32_t d = k2a_ll_subs(h, rmax[c]);                           /* > 0 in a half where h is a new row maximum */
+				const uint32_t hm = (REV && PK) ? h & cmask : h;                      /* REV: 0 in a half whose rectangle ends before jj */
+				const uint32_t d = k2a_ll_subs(hm, rmax[c]);                          /* > 0 in a half where h is a new row maximum */
 				const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
-				rmax[c] = k2a_ll_max(rmax[c], h);
+				rmax[c] = k2a_ll_max(rmax[c], hm);
 				rcol[c] = (jj2 & mask) | (rcol[c] & ~mask);
 			} else {
 				const int t = (int)hd + (int)smax - (int)pen;                          /* e, f >= 0: h >= 0 without a clamp */
@@ -186,7 +211,7 @@ struct K2aLaneLL {
 				const int s = (int)(PK ? (rmax[c] >> (16 * h)) & 0xffffu : rmax[c]);
 				const int j = (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
 				const int te = swapped ? j : i, qe = swapped ? i : j;
-				const bool take = i < nrows && s > 0 && k2a_ll_better(s, te, qe, key[h]);
+				const bool take = i < (REV ? rl[REV ? h : 0] : nrows) && s > 0 && k2a_ll_better(s, te, qe, key[h]);
 				key[h].s = take ? s : key[h].s;
 				key[h].te = take ? te : key[h].te;
 				key[h].qe = take ? qe : key[h].qe;

@@ -175,6 +175,13 @@ int k2a_shim_launch_compact(const K2aPair *pairs, const K2aResult *res, const ui
  * generation boundary at scratch + boff (8 bytes per column).  res[tasks[t].res[h]] = score, qe, te. */
 int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                        uint8_t *scratch, K2aLLRes *res, void *stream);
+/* Start-cell pass of ksw2amd_ll_align_batch, on the SAME task table, tables, sequences and scratch, behind the forward launch in
+ * `stream`: half h of a task reads res[tasks[t].res[h]] from device memory and runs the local pass over its reversed prefixes
+ * reverse(rows[0 .. re]) x reverse(columns[0 .. ce]); the two halves of a packed task run over their bounding rectangle.
+ * beg[tasks[t].res[h]] = that pass's score, qb, tb (score 0: 0, -1, -1, and tasks whose halves both scored 0 leave at once).
+ * Only ksw2_host_lla.c calls it (the simulator builds of tests/ll_util.py link the other host objects without it). */
+int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
 
 #ifdef __cplusplus
 }

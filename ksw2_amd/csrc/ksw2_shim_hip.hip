@@ -2169,11 +2169,15 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
 /* ---------------------------------------------------------------- local alignment (ksw2_lane_ll.h)
  * One task per wavefront (an int32 alignment, or two packed alignments of the same shape), four wavefronts per workgroup that
  * share the pen tables in LDS: [0, m*m) rows = target, [m*m, 2*m*m) rows = query (swapped tasks).  The per-step inputs of a lane --
- * its column code(s), and lane 0's boundary entry -- are loaded four steps ahead. */
-template<bool PK, bool LDSP>
-__global__ void __launch_bounds__(64 * K2A_WPB)
-k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
-              uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+ * its column code(s), and lane 0's boundary entry -- are loaded four steps ahead.
+ * REV (k2a_ll_rev_kernel): the start-cell pass of ksw2amd_ll_align_batch over the same task table.  Half h reads its forward result
+ * fres[tk.res[h]] and runs the reversed prefixes that end in that cell (limits and reversed indexing: K2aLaneLL<.., REV>); the task
+ * runs over the bounding rectangle of its halves, never more generations or steps than the forward launch, and a task whose halves
+ * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb. */
+template<bool PK, bool LDSP, bool REV>
+__device__ __forceinline__ void
+k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+            uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	extern __shared__ uint8_t k2a_ll_lds[];
 	const int mm = par.m * par.m;
@@ -2187,9 +2191,24 @@ k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, 
 	const uint8_t *r0 = seq + tk.roff[0], *r1 = seq + tk.roff[1 & -(int)PK];
 	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
 	uint2 *bnd = (uint2*)(scratch + tk.boff);
-	const int ncols = tk.ncols, ngen = (tk.nrows + K2A_LL_ROWS - 1) / K2A_LL_ROWS, nsteps = ncols + 63;
-	K2aLaneLL<PK, LDSP> L;
+	K2aLaneLL<PK, LDSP, REV> L;
 	L.init(par, tk, lane);
+	int fq[2] = { 0, 0 }, ft[2] = { 0, 0 };        /* REV: the forward end cells */
+	if (REV) {
+		int rl[2], cl[2];
+#pragma unroll
+		for (int h = 0; h < (PK ? 2 : 1); ++h) {
+			const K2aLLRes r = fres[tk.res[h]];
+			const bool pos = r.score > 0;
+			fq[h] = r.qe; ft[h] = r.te;
+			rl[h] = pos ? (tk.swapped ? r.qe : r.te) + 1 : 0;
+			cl[h] = pos ? (tk.swapped ? r.te : r.qe) + 1 : 0;
+			rl[h] = k2a_min(rl[h], tk.nrows); cl[h] = k2a_min(cl[h], tk.ncols);      /* a forward cell always lies inside; never trust it for an address */
+		}
+		L.set_limits(rl, cl);
+	}
+	const int ncols = REV ? L.ncols : tk.ncols, ngen = ((REV ? L.nrows : tk.nrows) + K2A_LL_ROWS - 1) / K2A_LL_ROWS, nsteps = ncols + 63;
+	const int cl0 = REV ? L.cl[0] : 0, cl1 = REV ? L.cl[PK && REV ? 1 : 0] : 0;
 	for (int g = 0; g < ngen; ++g) {
 		const bool from_bnd = g > 0, to_bnd = g + 1 < ngen;
 		if (from_bnd) {                                /* lane 63's boundary stores of the last generation before lane 0's loads */
@@ -2201,7 +2220,10 @@ k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, 
 		uint32_t qc[4], hb[4], eb[4];
 		auto fetch = [&](int k, uint32_t &q, uint32_t &h, uint32_t &e) {
 			const int jj = k2a_min(k2a_max(k - lane, 0), ncols - 1);
-			q = PK ? (uint32_t)c0[jj] | ((uint32_t)c1[jj] << 8) : (uint32_t)c0[jj];
+			if (REV) {                                 /* column jj of a half is c[cl - 1 - jj]; past its limit: its first byte */
+				const int j0 = k2a_max(cl0 - 1 - jj, 0), j1 = k2a_max(cl1 - 1 - jj, 0);
+				q = PK ? (uint32_t)c0[j0] | ((uint32_t)c1[j1] << 8) : (uint32_t)c0[j0];
+			} else q = PK ? (uint32_t)c0[jj] | ((uint32_t)c1[jj] << 8) : (uint32_t)c0[jj];
 			h = e = 0;
 			if (lane == 0 && from_bnd) { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
 		};
@@ -2238,10 +2260,32 @@ k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, 
 			k.s = take ? s : k.s; k.te = take ? te : k.te; k.qe = take ? qe : k.qe;
 		}
 		if (lane == 0 && (h == 0 || tk.res[1] != tk.res[0])) {
-			K2aLLRes r; r.score = k.s; r.qe = k.qe; r.te = k.te;
-			res[tk.res[h]] = r;
+			if (REV) {
+				const bool pos = k.s > 0;
+				K2aLLBeg b; b.score = k.s; b.qb = pos ? fq[h] - k.qe : -1; b.tb = pos ? ft[h] - k.te : -1;
+				beg[tk.res[h]] = b;
+			} else {
+				K2aLLRes r; r.score = k.s; r.qe = k.qe; r.te = k.te;
+				res[tk.res[h]] = r;
+			}
 		}
 	}
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+              uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                  uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
 extern "C" {
@@ -2694,6 +2738,22 @@ int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
 	else if (pk) hipLaunchKernelGGL((k2a_ll_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else hipLaunchKernelGGL((k2a_ll_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* start-cell pass of ksw2amd_ll_align_batch: the same grid over the same task table, behind the forward launch in the stream */
+int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ll_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (pk) hipLaunchKernelGGL((k2a_ll_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (lds) hipLaunchKernelGGL((k2a_ll_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_ll_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	CHECK(hipGetLastError());
 	return 0;
 }

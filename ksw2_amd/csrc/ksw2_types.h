@@ -201,5 +201,9 @@ typedef struct K2aLLTask {
 typedef struct K2aLLRes {
 	int32_t score, qe, te;           /* ksw2amd_lres_t */
 } K2aLLRes;
+/* start-cell pass (ksw2amd_ll_align_batch): the local pass over the reversed prefixes that end in (qe, te) */
+typedef struct K2aLLBeg {
+	int32_t score, qb, tb;           /* its best score (equals the forward score), qb = qe - qe', tb = te - te'; -1, -1 for a score of 0 */
+} K2aLLBeg;
 
 #endif

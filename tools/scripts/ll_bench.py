@@ -8,7 +8,15 @@ KSW2AMD_LL_FORM=0, its scores would fit the packed form).  Reports end-to-end GC
 download; best of --reps after one warm-up) and, when --kstats points at a `rocprofv3 --kernel-trace --stats` kernel_stats.csv of a run
 of the same workload with --kbatches ll_batch calls (1 + that run's --reps), resident GCUPS from the k2a_ll_kernel time per batch.
 The record names the kernel forms the batch took (the library's KSW2AMD_TRACE line).
-A parity sample (the scalar test oracle, tests/ll_oracle.c) is checked outside the clock."""
+A parity sample (the scalar test oracle, tests/ll_oracle.c) is checked outside the clock.
+
+  python tools/scripts/ll_bench.py --workload C --align cigar [--baseline] [--pairs N] [--out profiles/lla_bench_C.json]
+
+--align coords | cigar: ksw2amd_ll_align_batch (start cell, KSW_EZ_SCORE_ONLY; or with the CIGAR) instead of ksw2amd_ll_batch.
+--baseline: what a caller had to do before that entry existed, through the public API only -- ksw2amd_ll_batch, host reversal of the
+prefixes, a second ksw2amd_ll_batch, and for `cigar` ksw2amd_extz_batch on the intervals; timed the same way, and compared with the
+new entry's results outside the clock.  Rates stay in forward cells (qlen x tlen); rev_cells = sum of (qe + 1) x (te + 1) is recorded
+for the start-cell pass (its kernel: k2a_ll_rev_kernel in --kstats).  --pairs N: the first N pairs of the workload."""
 import argparse
 import csv
 import json
@@ -47,14 +55,44 @@ def workload(name, rng):
     return q, t
 
 
-def kernel_ms(path, batches):
-    """total k2a_ll_kernel time in a kernel_stats.csv, per batch"""
+def kernel_ms(path, batches, name="k2a_ll_kernel"):
+    """total time of the kernels whose name contains `name` in a kernel_stats.csv, per batch"""
     tot = 0.0
     with open(path) as f:
         for row in csv.DictReader(f):
-            if "k2a_ll_kernel" in row.get("Name", ""):
+            if name in row.get("Name", ""):
                 tot += float(row["TotalDurationNs"]) * 1e-6
     return tot / batches
+
+
+GENERIC_SC, SCORE_ONLY = 0x04, 0x01
+
+
+def align_new(lib, q, t, mat, gapo, gape, cigar):
+    r = lib.ll_align_batch(q, t, mat, gapo, gape, flag=0 if cigar else SCORE_ONLY)
+    return [(d["score"], d["qb"], d["qe"], d["tb"], d["te"], d["cigar"]) for d in r]
+
+
+def align_baseline(lib, q, t, mat, gapo, gape, cigar):
+    """the three-call pattern of a minimap2 / BWA style caller on the public API"""
+    f = lib.ll_batch(q, t, mat, gapo, gape)
+    pos = [i for i in range(len(q)) if f[i][0] > 0]
+    rq = [np.ascontiguousarray(q[i][:f[i][1] + 1][::-1]) for i in pos]
+    rt = [np.ascontiguousarray(t[i][:f[i][2] + 1][::-1]) for i in pos]
+    r = lib.ll_batch(rq, rt, mat, gapo, gape)
+    out = [(0, -1, -1, -1, -1, [])] * len(q)
+    cells = []
+    for k, i in enumerate(pos):
+        s, qe, te = map(int, f[i])
+        cells.append((i, s, qe - int(r[k][1]), qe, te - int(r[k][2]), te))
+    cig = [[]] * len(cells)
+    if cigar and cells:
+        ez = lib.extz_batch([q[i][qb:qe + 1] for i, s, qb, qe, tb, te in cells], [t[i][tb:te + 1] for i, s, qb, qe, tb, te in cells],
+                            mat, gapo, gape, w=-1, zdrop=-1, flag=GENERIC_SC)
+        cig = [z["cigar"] for z in ez]
+    for k, (i, s, qb, qe, tb, te) in enumerate(cells):
+        out[i] = (s, qb, qe, tb, te, cig[k])
+    return out
 
 
 def main():
@@ -65,10 +103,16 @@ def main():
     ap.add_argument("--kstats", default=None)
     ap.add_argument("--kbatches", type=int, default=2)
     ap.add_argument("--form", default=None, help="KSW2AMD_LL_FORM (default: 0 for D, the library's default otherwise)")
+    ap.add_argument("--align", choices=("coords", "cigar"), default=None, help="ksw2amd_ll_align_batch: start cells only, or with CIGARs")
+    ap.add_argument("--baseline", action="store_true", help="with --align: the three-call pattern on the public API instead")
+    ap.add_argument("--no-compare", action="store_true", help="with --align: skip the other path (a profiled run then holds 1 + reps batches of one path only)")
+    ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rng = np.random.default_rng(2024)
     q, t = workload(a.workload, rng)
+    if a.pairs > 0:
+        q, t = q[:a.pairs], t[:a.pairs]
     mat = u.simple_mat(5, 2, 4, -1)
     gapo, gape = 4, 2
     cells = float(sum(len(x) * len(y) for x, y in zip(q, t)))
@@ -76,6 +120,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.align:
+        return main_align(a, lib, q, t, mat, gapo, gape, cells, form)
     os.environ["KSW2AMD_TRACE"] = "1"                      # the form line on stderr (pk_tasks / int32_tasks)
     err_fd = os.dup(2)
     with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
@@ -107,6 +153,35 @@ def main():
         with open(a.out, "w") as f:
             json.dump(rec, f, indent=1)
     return 0 if ok else 1
+
+
+def main_align(a, lib, q, t, mat, gapo, gape, cells, form):
+    cigar = a.align == "cigar"
+    fn = align_baseline if a.baseline else align_new
+    res = fn(lib, q, t, mat, gapo, gape, cigar)                                  # warm-up
+    times = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        res = fn(lib, q, t, mat, gapo, gape, cigar)
+        times.append(time.perf_counter() - t0)
+    ok = None
+    if not a.no_compare:                                                           # outside the clock: both ways agree
+        ok = res == (align_new if a.baseline else align_baseline)(lib, q, t, mat, gapo, gape, cigar)
+    rev_cells = float(sum((r[2] + 1) * (r[4] + 1) for r in res if r[0] > 0))
+    rec = dict(workload=a.workload, mode="align-" + a.align, path="baseline" if a.baseline else "ll_align_batch", pairs=len(q), cells=cells,
+               rev_cells=rev_cells, e2e_s=min(times), e2e_gcups=cells / min(times) / 1e9, e2e_all_s=times, agrees_with_other_path=ok,
+               cigar_ops=int(sum(len(r[5]) for r in res)), ll_form=form)
+    if a.kstats:
+        fwd, rev = kernel_ms(a.kstats, a.kbatches, "k2a_ll_kernel"), kernel_ms(a.kstats, a.kbatches, "k2a_ll_rev_kernel")
+        allk = kernel_ms(a.kstats, a.kbatches, "")
+        rec.update(fwd_kernel_ms=fwd, rev_kernel_ms=rev, rev_over_fwd=rev / fwd if fwd else None, cigar_stage_kernel_ms=allk - fwd - rev,
+                   cigar_stage_share_of_e2e=(allk - fwd - rev) * 1e-3 / min(times),
+                   fwd_resident_gcups=cells / (fwd * 1e-3) / 1e9 if fwd else None, rev_resident_gcups=rev_cells / (rev * 1e-3) / 1e9 if rev else None)
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+    return 0 if ok is not False else 1
 
 
 if __name__ == "__main__":
