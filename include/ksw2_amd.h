@@ -313,6 +313,32 @@ int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
  * coordinates -1 and n_cigar = 0, and reports like ksw_ll_i16 */
 int ksw2amd_ll_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln);
 
+/* Flat local-alignment batches (new): every sequence lies in ONE arena -- host memory, or device memory of
+ * the calling thread's device -- and a pair is two offsets and two lengths.  res[i] / aln[i] are exactly what ksw2amd_ll_batch /
+ * ksw2amd_ll_align_batch return for the pair (base + qoff[i], qlen[i], base + toff[i], tlen[i]): tie rules, the (0, -1, -1) results,
+ * CIGAR buffer reuse through km and the flags included.  Offsets need no alignment; sequences may overlap or be shared between pairs
+ * (one query against many targets is one copy of the query).
+ * The library never walks over the arena's bytes on the host.  Host arena: the span of the arena that a chunk's pairs reference goes
+ * up as it is, in one copy, bytes between the sequences included (asynchronous and without staging when the arena is page-locked,
+ * ksw2amd_host_register).  Device arena (on_device != 0): nothing crosses the link for the two kernel passes; the CIGAR stage of
+ * ksw2amd_ll_align_batch_flat brings the span of the aligned intervals back to the host once.
+ * m, mat, the gap costs, NULL arrays, a negative n and the flag bits are checked on the host before anything is uploaded.  Residue
+ * codes are checked ON THE DEVICE, chunk by chunk, before any alignment kernel of the chunk is launched (only the bytes of referenced
+ * sequences: a byte >= m between two sequences is not an error).  A code >= m: KSW2AMD_E_PARAM, ksw2amd_last_error() names the lowest
+ * offending pair of that chunk, no alignment kernel has run on the chunk, and the entries of that chunk and of every later one hold
+ * the reset values (score 0, coordinates -1, n_cigar 0).  Large batches are cut into chunks (pairs in order; about 3 GB of sequence, or
+ * KSW2AMD_LL_CHUNK_BYTES when that is lower): res[] of EARLIER chunks of such a call may already hold results when a later chunk fails
+ * (ksw2amd_ll_align_batch_flat resets every entry).  Limit: the task table addresses a chunk's span with 32 bits, so the two
+ * sequences of ONE pair must lie within 4 GiB of each other in the arena (KSW2AMD_E_PARAM otherwise); pairs may lie anywhere. */
+typedef struct {
+	const uint8_t *base;            /* the arena: host memory, or device memory of the calling thread's device */
+	const uint64_t *qoff, *toff;    /* [n] byte offsets; any alignment; sequences may overlap or be shared between pairs */
+	const int32_t *qlen, *tlen;     /* [n] */
+	int32_t on_device;
+} ksw2amd_lflat_t;
+int ksw2amd_ll_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
+int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
+
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t
  * or NULL), fetch = wait + download + fill ez[]. */

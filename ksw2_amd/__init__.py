@@ -66,6 +66,12 @@ class LocalAln(ctypes.Structure):
                 ("m_cigar", ctypes.c_int32), ("n_cigar", ctypes.c_int32), ("cigar", ctypes.POINTER(ctypes.c_uint32))]
 
 
+class LocalFlat(ctypes.Structure):
+    """ksw2amd_lflat_t: one arena (host or device memory) + offsets and lengths of ksw2amd_ll_batch_flat / ksw2amd_ll_align_batch_flat."""
+    _fields_ = [("base", ctypes.c_void_p), ("qoff", ctypes.c_void_p), ("toff", ctypes.c_void_p), ("qlen", ctypes.c_void_p), ("tlen", ctypes.c_void_p),
+                ("on_device", ctypes.c_int32)]
+
+
 class Pair(ctypes.Structure):
     _fields_ = [("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("qlen", ctypes.c_int32), ("tlen", ctypes.c_int32),
                 ("w", ctypes.c_int32), ("zdrop", ctypes.c_int32), ("end_bonus", ctypes.c_int32), ("flag", ctypes.c_int32)]
@@ -98,7 +104,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat", "ksw2amd_host_register", "ksw2amd_host_unregister",
            "ksw2amd_device_alloc", "ksw2amd_device_free", "ksw2amd_device_upload", "ksw2amd_device_download", "ksw2amd_rerun_count",
            "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device",
-           "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align"]
+           "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align",
+           "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -106,7 +113,7 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_extz_batch", "ksw2amd_extd_batch", "ksw2amd_exts_batch", "ksw2amd_extf_batch", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device", "ksw2amd_plan_create",
                 "ksw2amd_sse_plan_create", "ksw2amd_exts_plan_create", "ksw2amd_extf_plan_create", "ksw2amd_plan_run",
                 "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
-                "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align"]
+                "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -239,6 +246,9 @@ class Library:
         if hasattr(L, "ksw2amd_ll_align_batch"):    # (nor have the simulator builds of tests/ll_util.py the start-cell pass)
             L.ksw2amd_ll_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
             L.ksw2amd_ll_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_ll_batch_flat"):     # (nor the flat entries and their check kernel's twin: tests/llf_util.py adds them)
+            L.ksw2amd_ll_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_ll_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -367,10 +377,9 @@ class Library:
         self.lib.ksw_extf2_sse(None, len(qa), qp, len(ta), tp, mch, mis, e, w, xdrop, ez)
         return ez_to_dict(ez, free_cigar=True)
 
-    def ll_batch(self, queries, targets, mat, gapo, gape, m=None):
-        """ksw2amd_ll_batch: best local (Smith-Waterman) score and end cell of every pair -> (n, 3) int32 array of score, qe, te."""
-        mat = np.ascontiguousarray(mat, dtype=np.int8)
-        m = int(round(len(mat) ** 0.5)) if m is None else m
+    @staticmethod
+    def local_pairs(queries, targets):
+        """A ksw2amd_lpair_t array over the given sequences -> (LocalPair array, the uint8 arrays it points into: keep them alive)."""
         n = len(queries)
         if len(targets) != n:
             raise ValueError("queries and targets differ in length")
@@ -380,11 +389,69 @@ class Library:
             qa, ta = keep[i], keep[n + i]
             pairs[i].query, pairs[i].target = qa.ctypes.data, ta.ctypes.data
             pairs[i].qlen, pairs[i].tlen = len(qa), len(ta)
+        return pairs, keep
+
+    def ll_batch(self, queries, targets, mat, gapo, gape, m=None, pairs=None, n=None):
+        """ksw2amd_ll_batch: best local (Smith-Waterman) score and end cell of every pair -> (n, 3) int32 array of score, qe, te.
+        pairs: a LocalPair array built beforehand (local_pairs) with n entries, used instead of queries / targets."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
         out = np.zeros((max(n, 1), 3), dtype=np.int32)
         rc = self.lib.ksw2amd_ll_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, n, pairs,
                                        out.ctypes.data_as(ctypes.POINTER(LocalResult)))
         self._check(rc)
         return out[:n]
+
+    @staticmethod
+    def _local_flat(base, qoff, qlen, toff, tlen, device_base):
+        """LocalFlat over numpy arrays (base: uint8 host arena, ignored for the bytes when device_base, a device address, is given)."""
+        qoff = np.ascontiguousarray(qoff, dtype=np.uint64)
+        toff = np.ascontiguousarray(toff, dtype=np.uint64)
+        qlen = np.ascontiguousarray(qlen, dtype=np.int32)
+        tlen = np.ascontiguousarray(tlen, dtype=np.int32)
+        n = len(qoff)
+        if not (len(toff) == len(qlen) == len(tlen) == n):
+            raise ValueError("offset and length arrays differ in length")
+        if device_base is None:
+            if not (isinstance(base, np.ndarray) and base.dtype == np.uint8 and base.flags.c_contiguous):
+                raise ValueError("base must be a contiguous uint8 array (it is borrowed, not copied)")
+        f = LocalFlat()
+        f.base = int(device_base) if device_base is not None else (base.ctypes.data if base.size else 0)
+        f.qoff, f.toff, f.qlen, f.tlen = qoff.ctypes.data, toff.ctypes.data, qlen.ctypes.data, tlen.ctypes.data
+        f.on_device = 1 if device_base is not None else 0
+        return f, n, (base, qoff, toff, qlen, tlen)
+
+    def ll_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, m=None, device_base=None, out=None):
+        """ksw2amd_ll_batch_flat: ll_batch on pairs given as offsets and lengths in one arena -- the uint8 array `base` (host memory;
+        page-lock it with host_register for asynchronous uploads) or, with device_base (an address from device_copy), device memory.
+        -> (n, 3) int32 array of score, qe, te.  out: an (>= n, 3) int32 array to write into (it holds the reset values after a failure)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1] == 3
+        rc = self.lib.ksw2amd_ll_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, n, ctypes.byref(f),
+                                            out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def ll_align_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, flag=0, m=None, device_base=None, aln=None):
+        """ksw2amd_ll_align_batch_flat(km=NULL, ...): ll_align_batch on an arena (see ll_batch_flat) -> list of dicts.  aln: a LocalAln
+        array that the caller keeps (CIGAR buffers are reused from call to call and stay the caller's to free)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_ll_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, flag, n, ctypes.byref(f), aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
 
     def ll_i16(self, query, target, mat, gapo, gape, m=None, size=2):
         """ksw_ll_qinit(NULL, size, ...) + ksw_ll_i16; the profile is released with libc free() -> (score, qe, te)."""
@@ -410,20 +477,14 @@ class Library:
             _libc.free(ctypes.cast(a.cigar, ctypes.c_void_p))
         return d
 
-    def ll_align_batch(self, queries, targets, mat, gapo, gape, flag=0, m=None):
+    def ll_align_batch(self, queries, targets, mat, gapo, gape, flag=0, m=None, pairs=None, n=None):
         """ksw2amd_ll_align_batch(km=NULL, ...): local alignment with start cell and CIGAR -> list of dicts score, qb, qe, tb, te,
         n_cigar, cigar (query[qb..qe] against target[tb..te], inclusive; flag: KSW_EZ_SCORE_ONLY / KSW_EZ_RIGHT / KSW_EZ_REV_CIGAR)."""
         mat = np.ascontiguousarray(mat, dtype=np.int8)
         m = int(round(len(mat) ** 0.5)) if m is None else m
-        n = len(queries)
-        if len(targets) != n:
-            raise ValueError("queries and targets differ in length")
-        keep = [np.ascontiguousarray(x, dtype=np.uint8) for x in list(queries) + list(targets)]
-        pairs = (LocalPair * max(n, 1))()
-        for i in range(n):
-            qa, ta = keep[i], keep[n + i]
-            pairs[i].query, pairs[i].target = qa.ctypes.data, ta.ctypes.data
-            pairs[i].qlen, pairs[i].tlen = len(qa), len(ta)
+        if pairs is None:            # (pairs: a prebuilt LocalPair array of n entries, as for ll_batch)
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
         aln = (LocalAln * max(n, 1))()
         rc = self.lib.ksw2amd_ll_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, flag, n, pairs, aln)
         out = [self._aln_to_dict(aln[i]) for i in range(n)]

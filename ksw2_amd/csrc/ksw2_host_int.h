@@ -50,6 +50,7 @@
 	X(EXTS_REG) \
 	X(LDSCODES) \
 	X(LDSROWS) \
+	X(LL_CHUNK_BYTES) \
 	X(LL_FORM) \
 	X(LL_LDS) \
 	X(LONG_MS) \
@@ -293,8 +294,23 @@ typedef int (*ll_rev_fn)(int pk, int lds, const K2aLL *par, const K2aLLTask *tas
 typedef struct {
 	int32_t size, qlen, m, pad;      /* ksw_ll_qinit's block: then qlen query codes, then m * m matrix entries */
 } ll_prof_t;
+/* flat local batches (ksw2_host_llf.c).  ll_check_fn = k2a_shim_launch_ll_check, passed in the same way: only ksw2_host_llf.o names it */
+typedef int (*ll_check_fn)(const K2aLLChk *ent, int nent, uint32_t nblocks, const uint8_t *seq, int m, uint32_t *bad, void *stream);
+/* where a chunk's sequences live: the caller's pairs, gathered into staging (pairs != NULL), or a borrowed arena (flat != NULL) */
+typedef struct {
+	const ksw2amd_lpair_t *pairs;      /* gathered: the chunk's pairs */
+	const ksw2amd_lflat_t *flat;       /* borrowed: the caller's arena and arrays, the chunk being pairs [first, first + n) */
+	int first;
+	uint64_t lo, hi;                   /* ... whose sequences lie in bytes [lo, hi) of the arena, hi - lo < 4 GiB */
+	ll_check_fn check;
+} ll_src_t;
+int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs);
+/* the stages of ksw2amd_ll_align_batch behind the two kernel passes (ksw2_host_lla.c), shared with ksw2amd_ll_align_batch_flat */
+#define LLA_FLAGS (KSW_EZ_SCORE_ONLY | KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)
+int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);
+int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln);
 #pragma GCC visibility pop
 #endif

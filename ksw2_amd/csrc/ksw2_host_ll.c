@@ -52,33 +52,68 @@ int ll_bad_code(const uint8_t *s, int len, int m)
 	return 0;
 }
 
-/* one chunk: pairs [0, n) of the caller's, all validated.  rev: the start-cell pass (beg[i] = its score, qb, tb), launched behind the
- * forward pass on the same task table, tables, sequences and results in device memory; one download brings back both arrays */
-static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res,
-                    ll_rev_fn rev, K2aLLBeg *beg)
+static inline int src_qlen(const ll_src_t *s, int i) { return s->flat ? s->flat->qlen[s->first + i] : s->pairs[i].qlen; }
+static inline int src_tlen(const ll_src_t *s, int i) { return s->flat ? s->flat->tlen[s->first + i] : s->pairs[i].tlen; }
+
+/* borrowed arenas: the check list of a chunk -- every distinct non-empty (offset, length) once, with the lowest pair that names it
+ * (a query shared by all pairs is scanned once).  ent[nent] is left for the sentinel; -1: allocation failed */
+static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
+{
+	const ksw2amd_lflat_t *f = src->flat;
+	size_t cap = 16, x;
+	uint32_t *tab;
+	int i, h, nent = 0;
+	while (cap < 4 * (size_t)n) cap <<= 1;
+	if (!(tab = (uint32_t*)calloc(cap, sizeof(uint32_t)))) return -1;
+	for (i = 0; i < n; ++i)
+		for (h = 0; h < 2; ++h) {
+			const int32_t len = h ? f->tlen[src->first + i] : f->qlen[src->first + i];
+			const uint64_t off = (h ? f->toff[src->first + i] : f->qoff[src->first + i]) - src->lo;
+			if (len <= 0) continue;
+			x = (size_t)((off * 0x9e3779b97f4a7c15ull ^ (uint64_t)(uint32_t)len * 0xc2b2ae3d27d4eb4full) >> 20) & (cap - 1);
+			while (tab[x] && (ent[tab[x] - 1].off != (uint32_t)off || ent[tab[x] - 1].len != (uint32_t)len)) x = (x + 1) & (cap - 1);
+			if (tab[x]) continue;
+			ent[nent].off = (uint32_t)off; ent[nent].len = (uint32_t)len; ent[nent].pair = (uint32_t)i; ent[nent].first = 0;
+			tab[x] = (uint32_t)++nent;
+		}
+	free(tab);
+	return nent;
+}
+
+/* one chunk: pairs [0, n) of the caller's.  Where the sequences live is all that differs between the two kinds of source:
+ *   gathered (src->pairs): validated by the caller, copied once each into the staging arena behind the task table and the pen tables;
+ *   borrowed (src->flat):  the chunk's span [lo, hi) of the caller's arena is the kernels' `seq` as it is -- uploaded in one copy
+ *     (host arena) or used in place (device arena) -- and the task table, the pen tables and the check list travel in a small buffer
+ *     of their own.  The residue codes are checked on the device (src->check) and the result word read before any alignment kernel
+ *     is launched; a code >= m ends the chunk with KSW2AMD_E_PARAM and every result at its reset value.
+ * rev: the start-cell pass (beg[i] = its score, qb, tb), launched behind the forward pass on the same task table, tables, sequences
+ * and results in device memory; one download brings back both arrays */
+int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg)
 {
 	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
+	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
-	uint8_t *h_arena = 0, *d_arena = 0, *d_scr = 0;
+	uint8_t *h_arena = 0, *d_arena = 0, *d_scr = 0, *d_span = 0;
+	const uint8_t *d_seq = 0;
 	K2aLLRes *h_res = 0, *d_res = 0;
 	const size_t res_bytes = (sizeof(K2aLLRes) + (rev ? sizeof(K2aLLBeg) : 0)) * (size_t)n;      /* K2aLLRes[n], then K2aLLBeg[n] */
-	size_t cap_h = 0, cap_d = 0, cap_s = 0, cap_hr = 0, cap_dr = 0;
-	int npk = 0, ni32 = 0, ntk_pk = 0, ntk = 0, i, rc = KSW2AMD_OK;
-	size_t tab_off, seq_off, bytes, scr = 0;
+	size_t cap_h = 0, cap_d = 0, cap_s = 0, cap_hr = 0, cap_dr = 0, cap_sp = 0;
+	int npk = 0, ni32 = 0, ntk_pk = 0, ntk = 0, nent = 0, i, rc = KSW2AMD_OK;
+	size_t tab_off, seq_off, chk_off = 0, bad_off = 0, bytes, scr = 0;
 	void *st = thread_stream();
 	if (!pk || !i32) { free(pk); free(i32); return fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); }
 	for (i = 0; i < n; ++i) {
-		const ksw2amd_lpair_t *p = &pairs[i];
+		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
 		ll_sort_t s;
 		res[i].score = 0; res[i].qe = res[i].te = -1;
 		if (rev) { beg[i].score = 0; beg[i].qb = beg[i].tb = -1; }
-		if (p->qlen <= 0 || p->tlen <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
-		s.rows = imax(p->qlen, p->tlen); s.cols = imin(p->qlen, p->tlen); s.sw = p->qlen > p->tlen; s.idx = (uint32_t)i;
+		if (ql <= 0 || tl <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
+		s.rows = imax(ql, tl); s.cols = imin(ql, tl); s.sw = ql > tl; s.idx = (uint32_t)i;
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
-		if (form > 0 && ll_pk_admit(p->qlen, p->tlen, smax)) pk[npk++] = s;
+		if (form > 0 && ll_pk_admit(ql, tl, smax)) pk[npk++] = s;
 		else i32[ni32++] = s;
 	}
 	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
@@ -98,20 +133,32 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 	qsort(pk, (size_t)ntk_pk, 2 * sizeof(ll_sort_t), cmp_cost);        /* tasks (pairs of entries) longest first */
 	qsort(i32, (size_t)ni32, sizeof(ll_sort_t), cmp_cost);
 	ntk = ntk_pk + ni32;
-	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers");
+	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers",
+	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host");
 	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] ll-rev: pk_tasks=%d int32_tasks=%d profile=%s\n", ntk_pk, ni32, lds ? "lds" : "registers");
-	if (ntk == 0) { free(pk); free(i32); return KSW2AMD_OK; }
-	/* arena: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once) */
+	if (ntk == 0 && !flat) { free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
+	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
+	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
 	seq_off = tab_off + align_up((size_t)2 * m * m, 256);
 	bytes = seq_off;
-	for (i = 0; i < npk; ++i) if (i % 2 == 0 || pk[i].idx != pk[i - 1].idx) bytes += align_up((size_t)pk[i].rows, 4) + align_up((size_t)pk[i].cols, 4);
-	for (i = 0; i < ni32; ++i) bytes += align_up((size_t)i32[i].rows, 4) + align_up((size_t)i32[i].cols, 4);
+	if (flat) {
+		chk_off = seq_off;
+		bad_off = chk_off + align_up(sizeof(K2aLLChk) * (2 * (size_t)n + 1), 256);
+		bytes = bad_off + 256;
+	} else {
+		for (i = 0; i < npk; ++i) if (i % 2 == 0 || pk[i].idx != pk[i - 1].idx) bytes += align_up((size_t)pk[i].rows, 4) + align_up((size_t)pk[i].cols, 4);
+		for (i = 0; i < ni32; ++i) bytes += align_up((size_t)i32[i].rows, 4) + align_up((size_t)i32[i].cols, 4);
+	}
 	h_arena = (uint8_t*)cache_get(BUF_HSEQ, bytes, &cap_h);
-	d_arena = (uint8_t*)cache_get(BUF_SEQ, bytes, &cap_d);
+	d_arena = (uint8_t*)cache_get(flat ? BUF_PAIRS : BUF_SEQ, bytes, &cap_d);
 	h_res = (K2aLLRes*)cache_get(BUF_HRES, res_bytes, &cap_hr);
 	d_res = (K2aLLRes*)cache_get(BUF_RES, res_bytes, &cap_dr);
-	if (!h_arena || !d_arena || !h_res || !d_res) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: buffer allocation failed: %s", k2a_shim_last_error()); goto out; }
+	if (flat && !flat->on_device && src->hi > src->lo) d_span = (uint8_t*)cache_get(BUF_SEQ, (size_t)(src->hi - src->lo), &cap_sp);
+	if (!h_arena || !d_arena || !h_res || !d_res || (flat && !flat->on_device && src->hi > src->lo && !d_span)) {
+		rc = fail(KSW2AMD_E_NOMEM, "local alignment: buffer allocation failed: %s", k2a_shim_last_error()); goto out;
+	}
+	d_seq = !flat ? d_arena : flat->on_device ? flat->base + src->lo : d_span;
 	tk = (K2aLLTask*)h_arena;
 	{
 		uint8_t *tab = h_arena + tab_off;
@@ -129,14 +176,19 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 			memset(k, 0, sizeof(*k));
 			for (h = 0; h < (is_pk ? 2 : 1); ++h) {
 				const ll_sort_t *s = is_pk ? &pk[2 * t + h] : &i32[t - ntk_pk];
-				const ksw2amd_lpair_t *p = &pairs[s->idx];
-				const int sw = p->qlen > p->tlen;                          /* rows = the longer sequence; the target on equal lengths */
-				const uint8_t *rs = sw ? p->query : p->target, *cs = sw ? p->target : p->query;
+				const int sw = s->sw;                                      /* rows = the longer sequence; the target on equal lengths */
 				k->nrows = s->rows; k->ncols = s->cols; k->swapped = sw;
 				k->res[h] = s->idx;
 				if (h == 1 && s->idx == k->res[0]) { k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; continue; }
-				k->roff[h] = (uint32_t)off; memcpy(h_arena + off, rs, (size_t)s->rows); off += align_up((size_t)s->rows, 4);
-				k->coff[h] = (uint32_t)off; memcpy(h_arena + off, cs, (size_t)s->cols); off += align_up((size_t)s->cols, 4);
+				if (flat) {                                                /* the chunk's span is below 4 GiB (ksw2_host_llf.c) */
+					const uint64_t qo = flat->qoff[src->first + s->idx] - src->lo, to = flat->toff[src->first + s->idx] - src->lo;
+					k->roff[h] = (uint32_t)(sw ? qo : to); k->coff[h] = (uint32_t)(sw ? to : qo);
+				} else {
+					const ksw2amd_lpair_t *p = &src->pairs[s->idx];
+					const uint8_t *rs = sw ? p->query : p->target, *cs = sw ? p->target : p->query;
+					k->roff[h] = (uint32_t)off; memcpy(h_arena + off, rs, (size_t)s->rows); off += align_up((size_t)s->rows, 4);
+					k->coff[h] = (uint32_t)off; memcpy(h_arena + off, cs, (size_t)s->cols); off += align_up((size_t)s->cols, 4);
+				}
 			}
 			if (!is_pk) { k->res[1] = k->res[0]; k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; }
 			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * 8, 256); }
@@ -146,14 +198,37 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 		d_scr = (uint8_t*)cache_get(BUF_TB, scr, &cap_s);
 		if (!d_scr) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: scratch allocation failed: %s", k2a_shim_last_error()); goto out; }
 	}
+	if (flat) {
+		/* the check: blocks are cut at 16-byte aligned ADDRESSES of the memory the kernel reads (ksw2_lane_llchk.h) */
+		K2aLLChk *ent = (K2aLLChk*)(h_arena + chk_off);
+		uint32_t *h_bad = (uint32_t*)(h_arena + bad_off);
+		uint64_t nblk = 0;
+		char msg[32];
+		if ((nent = ll_check_list(src, n, ent)) < 0) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
+		for (i = 0; i < nent; ++i) { ent[i].first = (uint32_t)nblk; nblk += K2A_LLCHK_BLOCKS((uint32_t)(((uintptr_t)d_seq + ent[i].off) & 15u), ent[i].len); }
+		ent[nent].off = ent[nent].len = 0; ent[nent].pair = K2A_LLCHK_NONE; ent[nent].first = (uint32_t)nblk;
+		if (nblk > 0xffffffffu) { rc = fail(KSW2AMD_E_PARAM, "local alignment: a chunk's sequences exceed the check's block count%s", ""); goto out; }
+		*h_bad = K2A_LLCHK_NONE;
+		if (k2a_shim_h2d(d_arena, h_arena, bytes, st)
+		    || (d_span && k2a_shim_h2d(d_span, flat->base + src->lo, (size_t)(src->hi - src->lo), st))
+		    || src->check((const K2aLLChk*)(d_arena + chk_off), nent, (uint32_t)nblk, d_seq, m, (uint32_t*)(d_arena + bad_off), st)
+		    || k2a_shim_d2h(h_bad, d_arena + bad_off, sizeof(uint32_t), st)
+		    || k2a_shim_stream_sync(st)) { rc = fail(KSW2AMD_E_NODEVICE, "local alignment: %s", k2a_shim_last_error()); goto out; }
+		if (*h_bad != K2A_LLCHK_NONE) {                   /* no alignment kernel has been launched on this chunk */
+			snprintf(msg, sizeof(msg), "%d", src->first + (int)*h_bad);
+			rc = fail(KSW2AMD_E_PARAM, "local alignment: pair %s: residue code >= m", msg);
+			goto out;
+		}
+		if (ntk == 0) goto out;
+	}
 	{
 		K2aLL par;
 		par.m = m; par.smax = smax; par.oe = gapo + gape; par.ge = gape;
-		if (k2a_shim_h2d(d_arena, h_arena, bytes, st)
-		    || k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_arena, d_arena + tab_off, d_scr, d_res, st)
-		    || k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_arena, d_arena + tab_off, d_scr, d_res, st)
-		    || (rev && rev(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_arena, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
-		    || (rev && rev(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_arena, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
+		if ((!flat && k2a_shim_h2d(d_arena, h_arena, bytes, st))
+		    || k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, st)
+		    || k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, st)
+		    || (rev && rev(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
+		    || (rev && rev(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
 		    || k2a_shim_d2h(h_res, d_res, res_bytes, st)
 		    || k2a_shim_stream_sync(st)) { rc = fail(KSW2AMD_E_NODEVICE, "local alignment: %s", k2a_shim_last_error()); goto out; }
 	}
@@ -166,8 +241,9 @@ static int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int 
 	}
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
+	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);
 	if (h_arena) cache_put(BUF_HSEQ, h_arena, cap_h);
-	if (d_arena) cache_put(BUF_SEQ, d_arena, cap_d);
+	if (d_arena) cache_put(flat ? BUF_PAIRS : BUF_SEQ, d_arena, cap_d);
 	if (h_res) cache_put(BUF_HRES, h_res, cap_hr);
 	if (d_res) cache_put(BUF_RES, d_res, cap_dr);
 	free(pk); free(i32);
@@ -201,7 +277,12 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
 			b += pb;
 		}
-		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, pairs + beg, res + beg, rev, rev ? begs + beg : 0);
+		{
+			ll_src_t src;
+			memset(&src, 0, sizeof(src));
+			src.pairs = pairs + beg;
+			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0);
+		}
 		if (rc) return rc;
 		beg = end;
 	}

@@ -12,26 +12,12 @@
  */
 #include "ksw2_host_int.h"
 
-#define LLA_FLAGS (KSW_EZ_SCORE_ONLY | KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)
-
-int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+/* after stages 1 and 2: aln[i] = score and both cells, checked against each other (no CIGAR yet).  Returns through *na the pairs with a
+ * positive score */
+int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na_)
 {
-	ksw2amd_lres_t *res = 0;
-	K2aLLBeg *beg = 0;
-	ksw2amd_pair_t *pp = 0;
-	ksw_extz_t *ez = 0;
-	int32_t *idx = 0;
-	int i, k, na = 0, rc;
+	int i, na = 0;
 	char msg[96];
-	/* every argument before anything is staged: the flag here, m / mat / gap costs / pair array / residue codes in ll_batch_ex */
-	if (flag & ~LLA_FLAGS) return fail(KSW2AMD_E_PARAM, "local alignment: flag accepts KSW_EZ_SCORE_ONLY, KSW_EZ_RIGHT and KSW_EZ_REV_CIGAR only%s", "");
-	if (n > 0 && !aln) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
-	if (n > 0) {
-		res = (ksw2amd_lres_t*)malloc(sizeof(*res) * (size_t)n);
-		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
-		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
-	}
-	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_ll_rev, beg)) != KSW2AMD_OK) goto out;
 	for (i = 0; i < n; ++i) {
 		ksw2amd_laln_t *a = &aln[i];
 		a->score = res[i].score; a->qe = res[i].qe; a->te = res[i].te; a->qb = beg[i].qb; a->tb = beg[i].tb;
@@ -40,22 +26,30 @@ int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
 		/* (qe, te) is the only cell of its prefix rectangle that holds the score, so the reversed pass finds the same one */
 		if (beg[i].score != res[i].score || beg[i].qb < 0 || beg[i].qb > res[i].qe || beg[i].tb < 0 || beg[i].tb > res[i].te) {
 			snprintf(msg, sizeof(msg), "%d: forward %d, reversed %d", i, res[i].score, beg[i].score);
-			rc = fail(KSW2AMD_E_NODEVICE, "local alignment: internal error, start-cell pass disagrees with the forward pass on pair %s", msg);
-			goto out;
+			return fail(KSW2AMD_E_NODEVICE, "local alignment: internal error, start-cell pass disagrees with the forward pass on pair %s", msg);
 		}
 		++na;
 	}
-	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
-	/* stage 3: the sub-ranges as extension pairs into the caller's sequences; the caller's CIGAR buffers travel through ez[] and back */
-	pp = (ksw2amd_pair_t*)malloc(sizeof(*pp) * (size_t)na);
-	ez = (ksw_extz_t*)calloc((size_t)na, sizeof(*ez));
-	idx = (int32_t*)malloc(sizeof(*idx) * (size_t)na);
+	*na_ = na;
+	return KSW2AMD_OK;
+}
+
+/* stage 3 for the na pairs of aln[] with a positive score: the sub-ranges as extension pairs into HOST memory; the caller's CIGAR
+ * buffers travel through ez[] and back.  at_start = 0: pairs[i] are the full sequences; 1: pairs[i].query / .target already point at
+ * residues qb / tb (ksw2_host_llf.c: the intervals of a device arena, brought back) */
+int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln)
+{
+	ksw2amd_pair_t *pp = (ksw2amd_pair_t*)malloc(sizeof(*pp) * (size_t)na);
+	ksw_extz_t *ez = (ksw_extz_t*)calloc((size_t)na, sizeof(*ez));
+	int32_t *idx = (int32_t*)malloc(sizeof(*idx) * (size_t)na);
+	int i, k, rc;
+	char msg[96];
 	if (!pp || !ez || !idx) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	for (i = 0, k = 0; i < n; ++i) {
 		const ksw2amd_laln_t *a = &aln[i];
 		if (a->score <= 0) continue;
-		pp[k].query = pairs[i].query + a->qb; pp[k].qlen = a->qe - a->qb + 1;
-		pp[k].target = pairs[i].target + a->tb; pp[k].tlen = a->te - a->tb + 1;
+		pp[k].query = pairs[i].query + (at_start ? 0 : a->qb); pp[k].qlen = a->qe - a->qb + 1;
+		pp[k].target = pairs[i].target + (at_start ? 0 : a->tb); pp[k].tlen = a->te - a->tb + 1;
 		pp[k].w = -1; pp[k].zdrop = -1; pp[k].end_bonus = 0;
 		pp[k].flag = KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR));
 		ez[k].cigar = a->cigar; ez[k].m_cigar = a->m_cigar;
@@ -77,7 +71,29 @@ int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
 			rc = fail(KSW2AMD_E_NODEVICE, "local alignment: internal error, the interval's global score differs from the local score on pair %s", msg);
 		}
 out:
-	free(res); free(beg); free(pp); free(ez); free(idx);
+	free(pp); free(ez); free(idx);
+	return rc;
+}
+
+int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+{
+	ksw2amd_lres_t *res = 0;
+	K2aLLBeg *beg = 0;
+	int na = 0, rc;
+	/* every argument before anything is staged: the flag here, m / mat / gap costs / pair array / residue codes in ll_batch_ex */
+	if (flag & ~LLA_FLAGS) return fail(KSW2AMD_E_PARAM, "local alignment: flag accepts KSW_EZ_SCORE_ONLY, KSW_EZ_RIGHT and KSW_EZ_REV_CIGAR only%s", "");
+	if (n > 0 && !aln) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	if (n > 0) {
+		res = (ksw2amd_lres_t*)malloc(sizeof(*res) * (size_t)n);
+		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
+		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
+	}
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_ll_rev, beg)) != KSW2AMD_OK) goto out;
+	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
+	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
+	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln);
+out:
+	free(res); free(beg);
 	return rc;
 }
 

@@ -182,6 +182,11 @@ int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
  * Only ksw2_host_lla.c calls it (the simulator builds of tests/ll_util.py link the other host objects without it). */
 int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+/* Residue-code check of the flat local-alignment batches (ksw2_lane_llchk.h), launched in `stream` before the chunk's alignment
+ * kernels: ent[nent + 1] lists the chunk's distinct sequences (offsets into seq) and numbers their 16-byte blocks, nblocks =
+ * ent[nent].first.  *bad, a device word the host set to K2A_LLCHK_NONE, ends up as the lowest ent[].pair with a code >= m.
+ * Only ksw2_host_llf.c calls it (the simulator builds of tests/ll_util.py and tests/lla_util.py have no such symbol). */
+int k2a_shim_launch_ll_check(const K2aLLChk *ent, int nent, uint32_t nblocks, const uint8_t *seq, int m, uint32_t *bad, void *stream);
 
 #ifdef __cplusplus
 }

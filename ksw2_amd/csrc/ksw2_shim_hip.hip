@@ -21,6 +21,7 @@
 #include "ksw2_lane_ssecb.h"
 #include "ksw2_lane_extfb.h"
 #include "ksw2_lane_ll.h"
+#include "ksw2_lane_llchk.h"
 
 #define K2A_WPB 4          /* wavefronts per workgroup; waves never synchronise with each other */
 /* The traceback walk is a chain of dependent loads and a few dozen instructions per step on ONE lane; what it needs is many
@@ -2288,6 +2289,24 @@ k2a_ll_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntas
 	k2a_ll_task<PK, LDSP, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
+/* ---------------------------------------------------------------- residue-code check of the flat local batches (ksw2_lane_llchk.h)
+ * One streaming pass over the distinct sequences of a chunk, before any alignment kernel of it: a wavefront takes K2A_LLCHK_WAVE
+ * consecutive 16-byte blocks of the entry list (work is spread by bytes), finds the entries of its first and last block once, and
+ * every lane tests four blocks.  A wavefront that saw a code >= m reduces its lanes' lowest pair and issues ONE atomic min into *bad. */
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_check_kernel(const K2aLLChk *__restrict__ ent, int nent, uint32_t nblocks, const uint8_t *__restrict__ seq, uint32_t m, uint32_t *__restrict__ bad)
+{
+	const uint32_t wave = blockIdx.x * K2A_WPB + (uint32_t)k2a_wave_id<true>();
+	const int lane = threadIdx.x & 63;
+	if ((uint64_t)wave * K2A_LLCHK_WAVE >= nblocks) return;
+	const uint32_t c0 = wave * K2A_LLCHK_WAVE, c1 = (nblocks - c0 > K2A_LLCHK_WAVE ? c0 + K2A_LLCHK_WAVE : nblocks) - 1;
+	const int elo = k2a_llchk_find(ent, 0, nent - 1, c0), ehi = k2a_llchk_find(ent, elo, nent - 1, c1);
+	uint32_t best = k2a_llchk_lane(ent, elo, ehi, c0, c1, lane, seq, m);
+	if (__builtin_amdgcn_ballot_w64(best != K2A_LLCHK_NONE) == 0) return;
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)best, d); best = o < best ? o : best; }
+	if (lane == 0) atomicMin(bad, best);
+}
+
 extern "C" {
 
 const char *k2a_shim_backend(void) { return "hip:gfx950"; }
@@ -2754,6 +2773,17 @@ int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *t
 	else if (pk) hipLaunchKernelGGL((k2a_ll_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else hipLaunchKernelGGL((k2a_ll_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* residue-code check of a flat local batch's chunk: *bad (device word, K2A_LLCHK_NONE before the launch) = the lowest pair with a code >= m */
+int k2a_shim_launch_ll_check(const K2aLLChk *ent, int nent, uint32_t nblocks, const uint8_t *seq, int m, uint32_t *bad, void *stream)
+{
+	if (nent <= 0 || nblocks == 0) return 0;
+	if (m < 1 || m > K2A_MAXM) { snprintf(g_err, sizeof(g_err), "local alignment: bad m"); return -1; }
+	const uint32_t waves = (nblocks + K2A_LLCHK_WAVE - 1) / K2A_LLCHK_WAVE;
+	hipLaunchKernelGGL(k2a_ll_check_kernel, dim3((waves + K2A_WPB - 1) / K2A_WPB), dim3(64 * K2A_WPB), 0, (hipStream_t)stream, ent, nent, nblocks, seq, (uint32_t)m, bad);
 	CHECK(hipGetLastError());
 	return 0;
 }

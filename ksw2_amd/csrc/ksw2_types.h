@@ -205,5 +205,16 @@ typedef struct K2aLLRes {
 typedef struct K2aLLBeg {
 	int32_t score, qb, tb;           /* its best score (equals the forward score), qb = qe - qe', tb = te - te'; -1, -1 for a score of 0 */
 } K2aLLBeg;
+/* residue-code check of the flat local-alignment batches (ksw2amd_ll_batch_flat; ksw2_lane_llchk.h): one entry per DISTINCT sequence
+ * that a chunk's pairs reference, cut into 16-byte blocks at 16-byte aligned addresses; entry [nent] is a sentinel whose first = the
+ * block total */
+typedef struct K2aLLChk {
+	uint32_t off, len;               /* arena byte offset and length (> 0) of the sequence */
+	uint32_t pair;                   /* lowest pair of the chunk that references it */
+	uint32_t first;                  /* index of its first block: the blocks of all entries before it */
+} K2aLLChk;
+#define K2A_LLCHK_NONE 0xffffffffu     /* the result word while no code >= m has been seen */
+#define K2A_LLCHK_BLOCKS(a_mod16, len) (((uint64_t)(a_mod16) + (len) + 15u) >> 4)      /* blocks of a sequence whose first byte has address a */
+#define K2A_LLCHK_WAVE 256             /* blocks (4 KiB) per wavefront: four per lane */
 
 #endif

@@ -16,8 +16,16 @@ A parity sample (the scalar test oracle, tests/ll_oracle.c) is checked outside t
 --baseline: what a caller had to do before that entry existed, through the public API only -- ksw2amd_ll_batch, host reversal of the
 prefixes, a second ksw2amd_ll_batch, and for `cigar` ksw2amd_extz_batch on the intervals; timed the same way, and compared with the
 new entry's results outside the clock.  Rates stay in forward cells (qlen x tlen); rev_cells = sum of (qe + 1) x (te + 1) is recorded
-for the start-cell pass (its kernel: k2a_ll_rev_kernel in --kstats).  --pairs N: the first N pairs of the workload."""
+for the start-cell pass (its kernel: k2a_ll_rev_kernel in --kstats).  --pairs N: the first N pairs of the workload.
+
+  python tools/scripts/ll_bench.py --workload A --flat all [--align coords] [--out profiles/llf_bench_A.json]
+
+--flat host | host-pinned | device | all: ksw2amd_ll_batch_flat (with --align coords: ksw2amd_ll_align_batch_flat, KSW_EZ_SCORE_ONLY)
+from one arena, against the unchanged pointer entry on the same pairs.  On both sides the clock covers ONLY the library call: the
+ksw2amd_lpair_t array, the arena, the offset arrays, page-locking and the device copy are made before it.  --no-compare skips the
+pointer entry (a profiled run then holds 1 + reps batches of one path); --kstats adds k2a_ll_check_kernel next to k2a_ll_kernel."""
 import argparse
+import ctypes
 import csv
 import json
 import os
@@ -95,6 +103,89 @@ def align_baseline(lib, q, t, mat, gapo, gape, cigar):
     return out
 
 
+def main_flat(a, lib, q, t, mat, gapo, gape, cells, form):
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    align = a.align == "coords"
+    if a.align == "cigar":
+        raise SystemExit("--flat measures ll_batch and --align coords")
+    # everything the calls take, outside the clock
+    pairs, keep = lib.local_pairs(q, t)
+    lens = np.array([len(x) for x in q + t], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    base = np.concatenate(q + t).astype(np.uint8)
+    qoff, toff = np.ascontiguousarray(offs[:n]), np.ascontiguousarray(offs[n:])
+    qlen, tlen = np.ascontiguousarray(lens[:n].astype(np.int32)), np.ascontiguousarray(lens[n:].astype(np.int32))
+    res = np.zeros((n, 3), dtype=np.int32)
+    aln = (ksw2_amd.LocalAln * n)()
+    rp = res.ctypes.data_as(ctypes.POINTER(ksw2_amd.LocalResult))
+
+    def timed(fn):
+        rc = fn()                                              # warm-up
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            times.append(time.perf_counter() - t0)
+        out = np.array([(x.score, x.qb, x.qe, x.tb, x.te) for x in aln], dtype=np.int32) if align else res.copy()
+        return times, out
+
+    def pointer():
+        if align:
+            return L.ksw2amd_ll_align_batch(None, 5, mp.ctypes.data_as(i8p), gapo, gape, SCORE_ONLY, n, pairs, aln)
+        return L.ksw2amd_ll_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp)
+
+    rec = dict(workload=a.workload, mode="flat-align-coords" if align else "flat", pairs=n, cells=cells, arena_bytes=int(base.nbytes), ll_form=form,
+               clock="library call only: pair array, arena, offsets, page-locking and device copy are built before it")
+    ref = None
+    if not a.no_compare:
+        times, ref = timed(pointer)
+        rec["pointer"] = dict(e2e_s=min(times), e2e_gcups=cells / min(times) / 1e9, e2e_all_s=times)
+    ok = True
+    for kind in (("host", "host-pinned", "device") if a.flat == "all" else (a.flat,)):
+        f = ksw2_amd.LocalFlat()
+        f.qoff, f.toff, f.qlen, f.tlen = qoff.ctypes.data, toff.ctypes.data, qlen.ctypes.data, tlen.ctypes.data
+        f.base, f.on_device = base.ctypes.data, 0
+        dev = None
+        if kind == "host-pinned":
+            lib._check(L.ksw2amd_host_register(base.ctypes.data, base.nbytes))
+        elif kind == "device":
+            dev = lib.device_copy(base)
+            f.base, f.on_device = dev, 1
+
+        def flat():
+            if align:
+                return L.ksw2amd_ll_align_batch_flat(None, 5, mp.ctypes.data_as(i8p), gapo, gape, SCORE_ONLY, n, ctypes.byref(f), aln)
+            return L.ksw2amd_ll_batch_flat(5, mp.ctypes.data_as(i8p), gapo, gape, n, ctypes.byref(f), rp)
+        times, got = timed(flat)
+        if kind == "host-pinned":
+            L.ksw2amd_host_unregister(base.ctypes.data)
+        if dev is not None:
+            lib.device_free(dev)
+        same = None if ref is None else bool((got == ref).all())
+        ok = ok and same is not False
+        rec[kind] = dict(e2e_s=min(times), e2e_gcups=cells / min(times) / 1e9, e2e_all_s=times, equals_pointer_entry=same)
+        if ref is not None:
+            rec[kind]["speedup_over_pointer"] = rec["pointer"]["e2e_s"] / min(times)
+    if not align:
+        idx = np.linspace(0, n - 1, a.parity).astype(int)
+        exp = u.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, gapo, gape)
+        rec["parity_ok"] = bool((got[idx] == exp).all())
+        ok = ok and rec["parity_ok"]
+    if a.kstats:
+        fwd, chk = kernel_ms(a.kstats, a.kbatches, "k2a_ll_kernel"), kernel_ms(a.kstats, a.kbatches, "k2a_ll_check_kernel")
+        rec.update(fwd_kernel_ms=fwd, check_kernel_ms=chk, check_over_fwd=chk / fwd if fwd else None)
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True)
@@ -106,6 +197,8 @@ def main():
     ap.add_argument("--align", choices=("coords", "cigar"), default=None, help="ksw2amd_ll_align_batch: start cells only, or with CIGARs")
     ap.add_argument("--baseline", action="store_true", help="with --align: the three-call pattern on the public API instead")
     ap.add_argument("--no-compare", action="store_true", help="with --align: skip the other path (a profiled run then holds 1 + reps batches of one path only)")
+    ap.add_argument("--flat", choices=("host", "host-pinned", "device", "all"), default=None,
+                    help="ksw2amd_ll_batch_flat / _align_batch_flat from one arena against the pointer entry, library calls only in the clock")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -120,6 +213,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.flat:
+        return main_flat(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.align:
         return main_align(a, lib, q, t, mat, gapo, gape, cells, form)
     os.environ["KSW2AMD_TRACE"] = "1"                      # the form line on stderr (pk_tasks / int32_tasks)
