@@ -576,6 +576,42 @@ K2A_FN void k2a_wire2_expand(uint32_t w2, uint32_t out[4])
 	}
 }
 
+/* End of the span of `span` arena bytes that starts at b0 <= total, cut at `total` (the bytes a wavefront-task or a workgroup expands out
+ * of the upload).  Never b0 + span first: arenas of up to 0xffef0000 bytes are admitted, and for their last spans that sum does not
+ * fit 32 bits -- min() of the wrapped sum would leave the span empty and its pairs unexpanded. */
+K2A_FN uint32_t k2a_span_end(uint32_t b0, uint32_t span, uint32_t total) { return total - b0 < span ? total : b0 + span; }
+
+/* The look a wavefront-task of the packed kernels takes at its targets (K2aScoring.pk_tn1; ksw2_shim_hip.hip, "Target wildcards in the
+ * packed kernels"), shared with the simulator.  k2a_codes_above4: nonzero if a byte of a code dword is above 4 (an OR over dwords
+ * cannot tell 4 | 1 from 5).  k2a_scan_codes: the codes >= 4 among target bytes [0, n) as seen by lane gl of a group of G -- bit 0 = a
+ * byte with bit 2 set (the wildcard, 4: the task takes the TN build of its body), bit 1 = a code above 4 (handed back to the host);
+ * the caller ORs the lanes of the group. */
+K2A_FN uint32_t k2a_codes_above4(uint32_t d) { return (d & 0xf8f8f8f8u) | ((d >> 2) & (d | (d >> 1)) & 0x01010101u); }
+template<int G>
+K2A_FN uint32_t k2a_scan_codes(const uint8_t *__restrict__ t, int n, int gl)
+{
+	uint32_t acc = 0, hi = 0;
+	/* sixteen bytes per lane and round, the four loads in flight together (unaligned dword loads, as everywhere; the arena is readable
+	 * past a sequence's end -- what lies there is masked off) */
+	for (int x = gl * 16; x < n; x += G * 16) {
+		uint32_t d[4];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+		for (int y = 0; y < 4; ++y) __builtin_memcpy(&d[y], t + x + 4 * y, 4);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+		for (int y = 0; y < 4; ++y) {
+			const int left = n - (x + 4 * y);                  /* bytes of this dword inside the target */
+			const uint32_t v = left >= 4 ? d[y] : left > 0 ? d[y] & ((1u << (8 * left)) - 1u) : 0u;
+			acc |= v;
+			if (v & 0x04040404u) hi |= k2a_codes_above4(v);
+		}
+	}
+	return ((acc & 0x04040404u) ? 1u : 0u) | ((hi | (acc & 0xf8f8f8f8u)) ? 2u : 0u);
+}
+
 /* Uniform plans (K2aUniform): record of pair i, and the pieces wavefront-task wt of a streamed launch waits for -- the rules the
  * host's gather follows when it copies the sequences (ksw2_host_plan.c: uni_fill_range) */
 K2A_FN K2aPair k2a_uniform_pair(const K2aUniform &u, uint32_t i)

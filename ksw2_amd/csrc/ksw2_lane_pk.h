@@ -186,8 +186,8 @@ K2A_FN k2a_pk k2a_bit_mask(uint32_t bits, int c) { return ((bits >> c) & 1u) ? 0
 
 /* Target wildcard rows (K2aScoring.pk_tn1, round 6).  x = { tA, 0, tB, 0 }, the raw codes of a row:
  * k2a_tsel_wild: the row's selector with 0x0c ("byte 0x00": penalty 0) where the code has bit 2 set, the ordinary one elsewhere;
- * k2a_tn_fix: what such a row's candidate loses instead -- bit 3 of a selector byte marks the half (ordinary bytes are 0..7);
- * k2a_codes_above4: nonzero if a byte of a code dword is above 4 (an OR over dwords cannot tell 4 | 1 from 5). */
+ * k2a_tn_fix: what such a row's candidate loses instead -- bit 3 of a selector byte marks the half (ordinary bytes are 0..7).
+ * (k2a_codes_above4 and the wavefront-task's look at its targets, k2a_scan_codes: ksw2_lane.h) */
 K2A_FN uint32_t k2a_tsel_wild(uint32_t x)
 {
 	const uint32_t n = x & 0x00040004u;
@@ -198,7 +198,6 @@ K2A_FN k2a_pk k2a_tn_fix(k2a_pk cand, uint32_t sel, int tn1)
 	const uint32_t m = (sel >> 3) & 0x00010001u;                  /* 1 per half that holds a wildcard row */
 	return cand - m * ((uint32_t)(tn1 - 1) & 0xffu);              /* both halves with one 32-bit subtract (k2a_sub32: the low half does not borrow) */
 }
-K2A_FN uint32_t k2a_codes_above4(uint32_t d) { return (d & 0xf8f8f8f8u) | ((d >> 2) & (d | (d >> 1)) & 0x01010101u); }
 
 /* Direction flags of one row for both halves (traceback kernels, round 5).  Every decision of the reference's direction logic
  * (ksw2_extz.c:72-86 / 98-112, ksw2_extd.c:88-114 / 126-152) is the SIGN of a packed difference: s1..s4 = candidate - gap state in

@@ -227,7 +227,12 @@ struct K2aTbStage {
  * (Round 4 first ran these launches as persistent loops over a task counter: the loop cost the kernels 6-40 registers -- the
  * headline's a resident wavefront, 4 830 -> 4 610 GCUPS -- for nothing a wait in front of the body does not give.) */
 /* 2-bit wire format (ksw2_lane.h): arena bytes [b0, b1) -- whole pairs of `stride` bytes -- out of the upload, by `nl` lanes of which
- * this is lane `l`: sixteen codes per lane and round, then the pairs' escape entries (codes above 3: rare) on top of what was expanded */
+ * this is lane `l`: sixteen codes per lane and round, then the pairs' escape entries (codes above 3: rare) on top of what was expanded.
+ * An escape byte lies in a chunk that ANY of the nl lanes may have stored, so every chunk store has to be done before the first escape
+ * store.  WG = false: the nl = 64 lanes are one wavefront, whose stores stay in order (the fence keeps the compiler from moving them).
+ * WG = true: the lanes are a whole workgroup and only a barrier orders wavefront 0's last round in front of wavefront 1's escapes; every
+ * lane of the workgroup must make the call (b0, b1 are uniform). */
+template<bool WG>
 __device__ __forceinline__ void k2a_wire2_task(const uint8_t *__restrict__ src8, uint8_t *__restrict__ dst8, uint32_t b0, uint32_t b1, uint32_t stride, int l, int nl)
 {
 	const uint32_t *src = (const uint32_t*)(src8 + (b0 >> 2));
@@ -238,6 +243,7 @@ __device__ __forceinline__ void k2a_wire2_task(const uint8_t *__restrict__ src8,
 		dst[x] = make_uint4(o[0], o[1], o[2], o[3]);
 	}
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      /* the expanded bytes before the escapes' */
+	if (WG) __syncthreads();
 	const uint32_t np = (b1 - b0) / stride;
 	for (uint32_t idx = (uint32_t)l; idx < np * 8u; idx += (uint32_t)nl) {
 		const uint32_t pair = idx >> 3, e = idx & 7u;
@@ -274,8 +280,8 @@ __device__ __forceinline__ bool k2a_queue_wait(K2aQueueDesc *qd, int wt)
 	 * then the arena bytes this wavefront wrote are what it reads (release / acquire at agent scope: the L1 may hold lines of the
 	 * recycled arena that a neighbour's look past its own sequences brought in). */
 	if (qd->unp_bytes) {
-		const uint32_t b0 = (uint32_t)wt * qd->unp_bytes, b1 = min(b0 + qd->unp_bytes, qd->unp_total);
-		if ((qd->unp_fmt >> 30) == 2u) k2a_wire2_task(qd->unp_src, qd->unp_dst, b0, b1, qd->unp_fmt & 0x3fffffffu, (int)(threadIdx.x & 63), 64);
+		const uint32_t b0 = (uint32_t)wt * qd->unp_bytes, b1 = k2a_span_end(b0, qd->unp_bytes, qd->unp_total);
+		if ((qd->unp_fmt >> 30) == 2u) k2a_wire2_task<false>(qd->unp_src, qd->unp_dst, b0, b1, qd->unp_fmt & 0x3fffffffu, (int)(threadIdx.x & 63), 64);
 		else {
 			const uint32_t *src = (const uint32_t*)(qd->unp_src + (b0 >> 1));
 			uint2 *dst = (uint2*)(qd->unp_dst + b0);
@@ -310,30 +316,9 @@ __device__ __forceinline__ void k2a_cptab_fill(const K2aScoring &sc, uint32_t *t
  * (K2aLanePk<.., TN>).  That branch inside the plain build cost every batch 1-3 % (profiles/r6_ab_tn.txt); here the plain build is
  * the code of round 5, and only wavefronts that hold a wildcard pay.  K2A_SYNC_WN: "some lane of this wavefront holds a wildcard row",
  * refreshed where strips start and end.
- * k2a_scan_codes: the codes >= 4 among target bytes [0, n) as seen by lane gl of a group of G: bit 0 = the wildcard (4), bit 1 = a code
- * above 4 (reported like before: K2aResult.pad[0], the host re-runs the pair). */
+ * k2a_scan_codes (ksw2_lane.h, shared with the simulator): the codes >= 4 among target bytes [0, n) as seen by lane gl of a group of G:
+ * bit 0 = the wildcard (4), bit 1 = a code above 4 (reported like before: K2aResult.pad[0], the host re-runs the pair). */
 #define K2A_SYNC_WN(L) do { (L).wn = __builtin_amdgcn_ballot_w64((L).hasn != 0) != 0; } while (0)
-template<int G>
-__device__ __forceinline__ uint32_t k2a_scan_codes(const uint8_t *__restrict__ t, int n, int gl)
-{
-	uint32_t acc = 0, hi = 0;
-	/* sixteen bytes per lane and round, the four loads in flight together (unaligned dword loads, as everywhere; the arena is readable
-	 * past a sequence's end -- what lies there is masked off) */
-	for (int x = gl * 16; x < n; x += G * 16) {
-		uint32_t d[4];
-#pragma unroll
-		for (int y = 0; y < 4; ++y) __builtin_memcpy(&d[y], t + x + 4 * y, 4);
-#pragma unroll
-		for (int y = 0; y < 4; ++y) {
-			const int left = n - (x + 4 * y);                  /* bytes of this dword inside the target */
-			const uint32_t v = left >= 4 ? d[y] : left > 0 ? d[y] & ((1u << (8 * left)) - 1u) : 0u;
-			acc |= v;
-			if (v & 0x04040404u) hi |= k2a_codes_above4(v);
-		}
-	}
-	return ((acc & 0x04040404u) ? 1u : 0u) | ((hi | (acc & 0xf8f8f8f8u)) ? 2u : 0u);
-}
-
 /* Packed-int16 resident fill: two same-shape alignments per lane group (ksw2_lane_pk.h).  k2a_fill_pk_body = one wavefront-task, in the
  * plain build or the TN one (target wildcard rows, see k2a_scan_codes); scan = what the task's look at its targets found (TN: bit 1 per
  * lane = a code above 4 in its group's targets). */
@@ -2534,12 +2519,13 @@ k2a_wire4_expand_kernel(const uint32_t *__restrict__ src, uint2 *__restrict__ ds
 		dst[x] = make_uint2(lo, hi);
 	}
 }
-/* the 2-bit format: one workgroup per group of `ppb` pairs (k2a_wire2_task) */
+/* the 2-bit format: one workgroup per group of `ppb` pairs (k2a_wire2_task<true>: a workgroup barrier between the chunks and the
+ * escapes -- the guard is uniform across the workgroup, the grid covers the arena exactly) */
 __global__ void __launch_bounds__(256)
 k2a_wire2_expand_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t total, uint32_t stride, uint32_t ppb)
 {
-	const uint32_t b0 = blockIdx.x * ppb * stride, b1 = min(b0 + ppb * stride, total);
-	if (b0 < b1) k2a_wire2_task(src, dst, b0, b1, stride, (int)threadIdx.x, 256);
+	const uint32_t b0 = blockIdx.x * ppb * stride, b1 = k2a_span_end(b0, ppb * stride, total);
+	if (b0 < b1) k2a_wire2_task<true>(src, dst, b0, b1, stride, (int)threadIdx.x, 256);
 }
 /* the whole arena out of its upload (a streamed launch that was abandoned: the wavefront-tasks that never started have not expanded
  * their pairs); fmt / stride: K2aQueueDesc.unp_fmt */
@@ -2548,7 +2534,9 @@ int k2a_shim_launch_wire_expand(const uint8_t *src, uint8_t *dst, size_t bytes, 
 	if (fmt == 2) {
 		const uint32_t ppb = 16, npairs = (uint32_t)(bytes / stride);
 		if (npairs == 0) return 0;
-		/* (the escapes of a pair are written by the workgroup that expanded it, behind its own stores: k2a_wire2_task's fence) */
+		/* (the escapes of a pair are written by the workgroup that expanded it, behind ALL of the workgroup's chunk stores: the barrier
+		 * of k2a_wire2_task<true> -- a fence alone orders one wavefront's stores, and an escape byte of pair 15 lies in a chunk that
+		 * wavefront 0 stores in a round the other three do not run) */
 		hipLaunchKernelGGL(k2a_wire2_expand_kernel, dim3((npairs + ppb - 1) / ppb), dim3(256), 0, (hipStream_t)stream, src, dst, (uint32_t)bytes, stride, ppb);
 		CHECK(hipGetLastError());
 		return 0;

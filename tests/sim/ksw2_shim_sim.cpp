@@ -6,6 +6,7 @@
  * against the oracle in the CPU test tier.  It is never part of the product library libksw2_amd.so.
  */
 #include <assert.h>
+#include <atomic>
 #include <chrono>
 #include <vector>
 #include <cstdio>
@@ -47,11 +48,18 @@ static void sim_wire2_task(const uint8_t *src8, uint8_t *dst8, uint32_t b0, uint
 		}
 }
 
-/* what k2a_scan_codes reports as "a code above 4" (the wavefront-task's look at its targets on the device) */
-static bool sim_codes_above4(const uint8_t *t, int n)
+/* The wavefront-task's look at its targets as the kernels take it: k2a_scan_codes (ksw2_lane.h) for every lane of the group, then what
+ * any of them saw (the kernels' ballot).  Bit 0 in any group of the wavefront: the TN build of the body, else the plain one -- both are
+ * instantiated here as on the device (SIM_PLAIN_TB: also for the traceback modes), and g_bodies counts the wavefront-tasks that took
+ * each (k2a_sim_body_counts). */
+constexpr bool SIM_PLAIN_TB = true;
+static std::atomic<unsigned long long> g_bodies[2];
+template<int G>
+static uint32_t sim_scan_group(const uint8_t *t, int n)
 {
-	for (int i = 0; i < n; ++i) if (t[i] > 4) return true;
-	return false;
+	uint32_t s = 0;
+	for (int gl = 0; gl < G; ++gl) s |= k2a_scan_codes<G>(t, n, gl);
+	return s;
 }
 
 template<int G, int C, bool DUAL, int MODE>
@@ -131,13 +139,16 @@ static void sim_fill(const K2aScoring sc, const K2aPair *pairs, const uint32_t *
 	}
 }
 
-/* mirrors k2a_fill_pk_kernel */
+/* mirrors k2a_fill_pk_kernel: the launch (streamed launches, the look at the targets), then one wavefront-task in the plain or the TN build */
+template<int G, int C, bool DUAL, int MODE, bool RB, bool NOMAX, int LDSROW, bool DEFER, bool TN>
+static void sim_fill_pk_body(const K2aScoring &sc, const K2aPair *pairs, const uint32_t *order2, int ntasks, const uint8_t *seq, uint8_t *tb,
+                             K2aResult *res, int wv, bool scan_on, const uint32_t *gscan);
+
 template<int G, int C, bool DUAL, int MODE, bool RB, bool NOMAX, int LDSROW = 0, bool DEFER = false>
 static void sim_fill_pk(const K2aScoring sc, const K2aPair *pairs, const uint32_t *order2, int ntasks, const uint8_t *seq, uint8_t *tb,
                         K2aResult *res, K2aQueueDesc *qd)
 {
 	constexpr int NG = 64 / G;
-	typedef K2aLanePk<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, true> Lane;      /* the TN build everywhere: it is the plain one plus the wildcard rows (the device picks per wavefront-task, k2a_scan_codes) */
 	const int nwaves = (ntasks + NG - 1) / NG;
 	for (int wv = 0; wv < nwaves; ++wv) {
 		/* streamed launches (k2a_queue_wait): wavefront-tasks in grid order; the simulator's uploads are synchronous, so a piece
@@ -148,7 +159,7 @@ static void sim_fill_pk(const K2aScoring sc, const K2aPair *pairs, const uint32_
 			if (qd->abort) break;
 			if (qd->need[wv] > qd->wm[0]) { qd->abort = 1; break; }
 			if (qd->unp_bytes) {                                 /* 4-bit wire format: the wavefront-task expands its own pairs (k2a_queue_wait) */
-				const uint32_t b0 = (uint32_t)wv * qd->unp_bytes, b1 = std::min(b0 + qd->unp_bytes, qd->unp_total);
+				const uint32_t b0 = (uint32_t)wv * qd->unp_bytes, b1 = k2a_span_end(b0, qd->unp_bytes, qd->unp_total);
 				if ((qd->unp_fmt >> 30) == 2u) sim_wire2_task(qd->unp_src, qd->unp_dst, b0, b1, qd->unp_fmt & 0x3fffffffu);
 				else for (uint32_t x = 0; x < (b1 - b0) >> 3; ++x) {
 					uint32_t w4, lo, hi;
@@ -158,6 +169,38 @@ static void sim_fill_pk(const K2aScoring sc, const K2aPair *pairs, const uint32_
 				}
 			}
 		}
+		uint32_t gscan[NG];
+		bool any4 = false;
+		const bool scan_on = sc.pk_tn1 != 0;
+		for (int g = 0; g < NG; ++g) {
+			const int task = wv * NG + g;
+			gscan[g] = 0;
+			if (scan_on && task < ntasks) {
+				const K2aPair &pa = pairs[order2[2 * task]], &pb = pairs[order2[2 * task + 1]];
+				gscan[g] = sim_scan_group<G>(seq + pa.toff, pa.tlen_full) | sim_scan_group<G>(seq + pb.toff, pb.tlen_full);
+			}
+			any4 |= (gscan[g] & 1u) != 0;
+		}
+		if constexpr (SIM_PLAIN_TB || MODE == K2A_MODE_SCORE) {
+			if (!any4) {
+				++g_bodies[0];
+				sim_fill_pk_body<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, false>(sc, pairs, order2, ntasks, seq, tb, res, wv, scan_on, gscan);
+				continue;
+			}
+		}
+		++g_bodies[1];
+		sim_fill_pk_body<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, true>(sc, pairs, order2, ntasks, seq, tb, res, wv, scan_on, gscan);
+	}
+}
+
+/* mirrors k2a_fill_pk_body */
+template<int G, int C, bool DUAL, int MODE, bool RB, bool NOMAX, int LDSROW, bool DEFER, bool TN>
+static void sim_fill_pk_body(const K2aScoring &sc, const K2aPair *pairs, const uint32_t *order2, int ntasks, const uint8_t *seq, uint8_t *tb,
+                             K2aResult *res, int wv, bool scan_on, const uint32_t *gscan)
+{
+	constexpr int NG = 64 / G;
+	typedef K2aLanePk<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, TN> Lane;
+	{
 		static thread_local Lane L[64];
 		static thread_local uint32_t lrows[K2A_PK_LDSROW_WORDS(C)];
 		K2aBook book[NG][2];
@@ -285,7 +328,7 @@ static void sim_fill_pk(const K2aScoring sc, const K2aPair *pairs, const uint32_
 		for (int lane = 0; lane < 64; ++lane)
 			if (valid[lane] && lane % G == 0) {
 				bool gsaw = false;
-				if (sc.pk_tn1) gsaw = sim_codes_above4(seq + prA[lane].toff, prA[lane].tlen_full) || sim_codes_above4(seq + pairs[piB[lane]].toff, pairs[piB[lane]].tlen_full);      /* k2a_scan_codes */
+				if (scan_on) gsaw = (gscan[lane / G] & 2u) != 0;      /* k2a_scan_codes */
 				else for (int l = lane; l < lane + G; ++l) gsaw |= L[l].saw_wildcard();
 				k2a_finish(prA[lane], book[lane / G][0], &res[piA[lane]]);
 				if (piB[lane] != piA[lane]) k2a_finish(pairs[piB[lane]], book[lane / G][1], &res[piB[lane]]);
@@ -887,14 +930,14 @@ static void sim_ssec_blk(const K2aSsec P, const K2aPair *pairs, const uint32_t *
 /* mirrors k2a_fill_pkmp_kernel.  The generations of a task run one after the other here (on the device four wavefronts pipeline
  * them; the data flow -- boundary entries through `bnd`, row-maximum keys in the task's spill blocks, a re-base every
  * K2A_PKMP_T steps -- is the same, and so is every value). */
-template<bool DUAL, int MODE>
-static void sim_fill_pkmp(const K2aScoring sc, const K2aPair *pairs, const uint32_t *order2, int ntasks, const uint8_t *seq, uint8_t *tb,
-                          uint32_t *bnd, K2aResult *res)
+template<bool DUAL, int MODE, bool TN>
+static void sim_fill_pkmp_body(const K2aScoring &sc, const K2aPair *pairs, const uint32_t *order2, const uint8_t *seq, uint8_t *tb,
+                               uint32_t *bnd, K2aResult *res, int task)
 {
 	constexpr int C = 16, G = 64, W = K2A_PKMP_WAVES, T = K2A_PKMP_T, R = G * C;
-	typedef K2aLanePkMp<C, DUAL, MODE, true> Lane;
+	typedef K2aLanePkMp<C, DUAL, MODE, TN> Lane;
 	constexpr int WB = Lane::TBWORDS * 4;
-	for (int task = 0; task < ntasks; ++task) {
+	{
 		static thread_local Lane L[64];
 		const uint32_t piA = order2[2 * task], piB = order2[2 * task + 1];
 		const K2aPair prA = pairs[piA], prB = pairs[piB];
@@ -990,13 +1033,36 @@ static void sim_fill_pkmp(const K2aScoring sc, const K2aPair *pairs, const uint3
 	}
 }
 
-/* mirrors k2a_fill_solo_kernel: one alignment per wavefront, both halves of every lane */
-template<int C, bool DUAL, int MODE>
-static void sim_fill_solo(const K2aScoring sc, const K2aPair *pairs, const uint32_t *order, int ntasks, const uint8_t *seq, uint8_t *tb,
-                          K2aResult *res)
+/* mirrors k2a_fill_pkmp_kernel's choice: the workgroup looks at the task's two targets and takes the plain or the TN build of the body */
+template<bool DUAL, int MODE>
+static void sim_fill_pkmp(const K2aScoring sc, const K2aPair *pairs, const uint32_t *order2, int ntasks, const uint8_t *seq, uint8_t *tb,
+                          uint32_t *bnd, K2aResult *res)
 {
-	typedef K2aLaneSolo<C, DUAL, MODE, true> Lane;
 	for (int task = 0; task < ntasks; ++task) {
+		uint32_t scan = 0;
+		if (sc.pk_tn1) {
+			const K2aPair &pa = pairs[order2[2 * task]], &pb = pairs[order2[2 * task + 1]];
+			scan = sim_scan_group<64>(seq + pa.toff, pa.tlen_full) | sim_scan_group<64>(seq + pb.toff, pb.tlen_full);
+		}
+		if constexpr (SIM_PLAIN_TB || MODE == K2A_MODE_SCORE) {
+			if (!(scan & 1u)) {
+				++g_bodies[0];
+				sim_fill_pkmp_body<DUAL, MODE, false>(sc, pairs, order2, seq, tb, bnd, res, task);
+				continue;
+			}
+		}
+		++g_bodies[1];
+		sim_fill_pkmp_body<DUAL, MODE, true>(sc, pairs, order2, seq, tb, bnd, res, task);
+	}
+}
+
+/* mirrors k2a_fill_solo_body: one alignment per wavefront, both halves of every lane */
+template<int C, bool DUAL, int MODE, bool TN>
+static void sim_fill_solo_body(const K2aScoring &sc, const K2aPair *pairs, const uint32_t *order, const uint8_t *seq, uint8_t *tb,
+                               K2aResult *res, int task, bool scan_on, uint32_t scan)
+{
+	typedef K2aLaneSolo<C, DUAL, MODE, TN> Lane;
+	{
 		const uint32_t pi = order[task];
 		const K2aPair pr = pairs[pi];
 		static thread_local Lane L[64];
@@ -1051,9 +1117,30 @@ static void sim_fill_solo(const K2aScoring sc, const K2aPair *pairs, const uint3
 		}
 		k2a_finish(pr, book, &res[pi]);
 		bool saw = false;
-		if (sc.pk_tn1) saw = sim_codes_above4(seq + pr.toff, pr.tlen_full);      /* k2a_scan_codes */
+		if (scan_on) saw = (scan & 2u) != 0;      /* k2a_scan_codes */
 		else for (int l = 0; l < 64; ++l) saw |= L[l].saw_wildcard();
 		if (saw) res[pi].pad[0] = 1;
+	}
+}
+
+/* mirrors k2a_fill_solo_kernel: the wavefront-task looks at its target and takes the plain or the TN build of the body */
+template<int C, bool DUAL, int MODE>
+static void sim_fill_solo(const K2aScoring sc, const K2aPair *pairs, const uint32_t *order, int ntasks, const uint8_t *seq, uint8_t *tb,
+                          K2aResult *res)
+{
+	const bool scan_on = sc.pk_tn1 != 0;
+	for (int task = 0; task < ntasks; ++task) {
+		const K2aPair &pr = pairs[order[task]];
+		const uint32_t scan = scan_on ? sim_scan_group<64>(seq + pr.toff, pr.tlen_full) : 0u;
+		if constexpr (SIM_PLAIN_TB || MODE == K2A_MODE_SCORE) {
+			if (!(scan & 1u)) {
+				++g_bodies[0];
+				sim_fill_solo_body<C, DUAL, MODE, false>(sc, pairs, order, seq, tb, res, task, scan_on, scan);
+				continue;
+			}
+		}
+		++g_bodies[1];
+		sim_fill_solo_body<C, DUAL, MODE, true>(sc, pairs, order, seq, tb, res, task, scan_on, scan);
 	}
 }
 
@@ -1174,6 +1261,24 @@ static void sim_extf_win(const K2aExtf par, const K2aPair *pairs, const uint32_t
 
 extern "C" {
 
+/* test hooks of this library only (tests/test_wire_cpu.py): the shared span helper; the look at the targets for a whole group of G
+ * lanes with byte p (p0 <= p < n) of a copy of t[0, n + 16) set to `code`, one answer per p in out[p - p0]; and the wavefront-tasks
+ * that took the plain / the TN build of their body so far */
+uint32_t k2a_sim_span_end(uint32_t b0, uint32_t span, uint32_t total) { return k2a_span_end(b0, span, total); }
+int k2a_sim_scan_sweep(int G, const uint8_t *t, int n, int p0, int code, uint8_t *out)
+{
+	std::vector<uint8_t> buf(t, t + n + 16);
+	if (G != 8 && G != 16 && G != 64) return -1;
+	for (int p = p0; p < n; ++p) {
+		const uint8_t keep = buf[p];
+		buf[p] = (uint8_t)code;
+		out[p - p0] = (uint8_t)(G == 8 ? sim_scan_group<8>(buf.data(), n) : G == 16 ? sim_scan_group<16>(buf.data(), n) : sim_scan_group<64>(buf.data(), n));
+		buf[p] = keep;
+	}
+	return 0;
+}
+void k2a_sim_body_counts(unsigned long long out[2]) { out[0] = g_bodies[0]; out[1] = g_bodies[1]; }
+
 const char *k2a_shim_backend(void) { return "sim"; }
 const char *k2a_shim_last_error(void) { return g_err; }
 /* KSW2AMD_SIM_DEVICES=N pretends to have N devices (all the same host memory) so that the host's multi-device worker
@@ -1251,7 +1356,14 @@ int k2a_shim_launch_gather(const K2aGather *tab, int n, uint8_t *dst, void *)
 }
 int k2a_shim_launch_wire_expand(const uint8_t *src, uint8_t *dst, size_t bytes, int fmt, uint32_t stride, void *)
 {
-	if (fmt == 2) { sim_wire2_task(src, dst, 0, (uint32_t)(bytes / stride * stride), stride); return 0; }
+	if (fmt == 2) {                                               /* k2a_wire2_expand_kernel: one workgroup per 16 pairs */
+		const uint32_t ppb = 16, npairs = (uint32_t)(bytes / stride);
+		for (uint32_t blk = 0; blk < (npairs + ppb - 1) / ppb; ++blk) {
+			const uint32_t b0 = blk * ppb * stride, b1 = k2a_span_end(b0, ppb * stride, (uint32_t)bytes);
+			if (b0 < b1) sim_wire2_task(src, dst, b0, b1, stride);
+		}
+		return 0;
+	}
 	for (size_t x = 0; x < bytes >> 3; ++x) {
 		uint32_t w4, lo, hi;
 		memcpy(&w4, src + 4 * x, 4);
