@@ -339,6 +339,35 @@ typedef struct {
 int ksw2amd_ll_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
 int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
 
+/* Suboptimal local score (new): the member of the classic local-alignment record that BWA's
+ * ksw_align reports as kswr_t.score2 / te2 and SSW as score2 / ref_end2 -- the second-best score OUTSIDE the neighbourhood of the best
+ * hit, from which a caller derives a mapping quality or a repeat call.  With H(t, j) the matrix of ksw2amd_ll_batch (t: target index,
+ * j: query index), (score, qe, te) its result and R(t) = max_j H(t, j) the maximum of target row t:
+ *   d       = excl when excl >= 0, else ceil(score / smax), smax the largest matrix entry (BWA's default: an alignment that scores
+ *             `score` spans at least that many target rows); the rows with |t - te| <= d are excluded;
+ *   score2  = the largest R(t) over the rows that are not excluded;
+ *   te2     = the smallest such t that attains it;   qe2 = the smallest j with H(te2, j) == score2;
+ *   score2 == 0 (every row excluded, no positive cell outside the window, or score == 0): te2 = qe2 = -1.
+ * It is the plain maximum over rows: runs of adjacent rows are NOT merged into "peaks" as BWA does before it compares them, so a
+ * shoulder of the best alignment that reaches beyond the window counts.  res[i] is bit for bit what ksw2amd_ll_batch returns.
+ * Arguments as for ksw2amd_ll_batch (m 1..127, gapo / gape 0..127, every residue code < m) and excl <= 0x3fffffff, all checked before
+ * anything is launched: KSW2AMD_E_PARAM.  The flat entry takes an arena like ksw2amd_ll_batch_flat, with the same check on the device,
+ * the same chunks and the same error semantics; sub[] is reset together with res[].  Pairs that never reach the device (an empty
+ * sequence, a matrix without a positive entry) get (0, -1, -1).  ksw2amd_ll_align_batch does not carry the suboptimal score: compute
+ * it for all pairs here and ask for start and CIGAR on those you keep.  Cost: target rows are the matrix rows whatever the lengths, so
+ * a target much shorter than its query fills few lanes of a wavefront (ksw2amd_ll_batch would have turned the pair round). */
+typedef struct {
+	int32_t score2, qe2, te2;
+} ksw2amd_lsub_t;
+int ksw2amd_ll_sub_batch(int m, const int8_t *mat, int gapo, int gape, int excl, int n,
+                         const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ksw2amd_lsub_t *sub);
+int ksw2amd_ll_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int excl, int n,
+                              const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ksw2amd_lsub_t *sub);
+/* one pair on a ksw_ll_qinit profile; returns the score.  On a device failure or a bad argument it returns 0 with *qe = *te = -1 and
+ * *sub = (0, -1, -1), and reports like ksw_ll_i16 */
+int ksw2amd_ll_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int excl,
+                   int *qe, int *te, ksw2amd_lsub_t *sub);
+
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t
  * or NULL), fetch = wait + download + fill ez[]. */

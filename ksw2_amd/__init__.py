@@ -60,6 +60,11 @@ class LocalResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("qe", ctypes.c_int32), ("te", ctypes.c_int32)]
 
 
+class LocalSub(ctypes.Structure):
+    """ksw2amd_lsub_t: score2, qe2, te2 (ksw2amd_ll_sub_batch)."""
+    _fields_ = [("score2", ctypes.c_int32), ("qe2", ctypes.c_int32), ("te2", ctypes.c_int32)]
+
+
 class LocalAln(ctypes.Structure):
     """ksw2amd_laln_t: score, the alignment's first and last cell, CIGAR (ksw2amd_ll_align_batch)."""
     _fields_ = [("score", ctypes.c_int32), ("qb", ctypes.c_int32), ("qe", ctypes.c_int32), ("tb", ctypes.c_int32), ("te", ctypes.c_int32),
@@ -105,7 +110,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_device_alloc", "ksw2amd_device_free", "ksw2amd_device_upload", "ksw2amd_device_download", "ksw2amd_rerun_count",
            "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device",
            "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align",
-           "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat"]
+           "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
+           "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -113,7 +119,8 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_extz_batch", "ksw2amd_extd_batch", "ksw2amd_exts_batch", "ksw2amd_extf_batch", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device", "ksw2amd_plan_create",
                 "ksw2amd_sse_plan_create", "ksw2amd_exts_plan_create", "ksw2amd_extf_plan_create", "ksw2amd_plan_run",
                 "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
-                "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat"]
+                "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
+                "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -226,6 +233,10 @@ class Library:
         L.ksw2amd_device_upload.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         L.ksw2amd_device_download.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         L.ksw2amd_rerun_count.restype = ctypes.c_int64
+        if hasattr(L, "ksw2amd_ll_sub_batch"):      # (nor the suboptimal score and its reduction's twin: tests/lls_util.py adds them)
+            L.ksw2amd_ll_sub_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult), ctypes.POINTER(LocalSub)]
+            L.ksw2amd_ll_sub_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult), ctypes.POINTER(LocalSub)]
+            L.ksw2amd_ll_sub.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(LocalSub)]
         L.ksw2amd_set_small_call_cells.argtypes = [ctypes.c_int64]
         L.ksw2amd_set_small_call_cells.restype = None
         L.ksw2amd_small_call_count.restype = ctypes.c_long
@@ -452,6 +463,54 @@ class Library:
         out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
         self._check(rc)
         return out
+
+    def ll_sub_batch(self, queries, targets, mat, gapo, gape, excl=-1, m=None, pairs=None, n=None):
+        """ksw2amd_ll_sub_batch: ll_batch plus the suboptimal score -- the largest row maximum outside the target rows |t - te| <= d
+        (d = excl, or ceil(score / smax) for excl < 0) -> two (n, 3) int32 arrays: score, qe, te and score2, qe2, te2."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        sub = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_ll_sub_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, excl, n, pairs,
+                                           out.ctypes.data_as(ctypes.POINTER(LocalResult)), sub.ctypes.data_as(ctypes.POINTER(LocalSub)))
+        self._check(rc)
+        return out[:n], sub[:n]
+
+    def ll_sub_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, excl=-1, m=None, device_base=None, out=None, sub=None):
+        """ksw2amd_ll_sub_batch_flat: ll_sub_batch on an arena (see ll_batch_flat) -> two (n, 3) int32 arrays.  out / sub: (>= n, 3)
+        int32 arrays to write into (they hold the reset values after a failure)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        sub = np.zeros((max(n, 1), 3), dtype=np.int32) if sub is None else sub
+        for a in (out, sub):
+            assert a.dtype == np.int32 and a.flags.c_contiguous and a.shape[0] >= n and a.shape[1] == 3
+        rc = self.lib.ksw2amd_ll_sub_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, excl, n, ctypes.byref(f),
+                                                out.ctypes.data_as(ctypes.POINTER(LocalResult)), sub.ctypes.data_as(ctypes.POINTER(LocalSub)))
+        self._check(rc)
+        return out[:n], sub[:n]
+
+    def ll_sub(self, query, target, mat, gapo, gape, excl=-1, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_ll_sub -> (score, qe, te), (score2, qe2, te2)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        qa, qp = self._seq(query)
+        ta, tp = self._seq(target)
+        prof = self.lib.ksw_ll_qinit(None, size, len(qa), qp, m, mat.ctypes.data_as(_i8p))
+        if not prof:
+            raise Ksw2Error("ksw_ll_qinit: " + self.last_error())
+        try:
+            qe, te, s = _int(0), _int(0), LocalSub()
+            score = self.lib.ksw2amd_ll_sub(prof, len(ta), tp, gapo, gape, excl, ctypes.byref(qe), ctypes.byref(te), ctypes.byref(s))
+        finally:
+            _libc.free(prof)
+        return (int(score), qe.value, te.value), (int(s.score2), int(s.qe2), int(s.te2))
 
     def ll_i16(self, query, target, mat, gapo, gape, m=None, size=2):
         """ksw_ll_qinit(NULL, size, ...) + ksw_ll_i16; the profile is released with libc free() -> (score, qe, te)."""

@@ -304,10 +304,23 @@ typedef struct {
 	uint64_t lo, hi;                   /* ... whose sequences lie in bytes [lo, hi) of the arena, hi - lo < 4 GiB */
 	ll_check_fn check;
 } ll_src_t;
-int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg);
+/* suboptimal score (ksw2_host_lls.c).  launch = k2a_shim_launch_ll_sub, passed in the same way: only ksw2_host_lls.o names it.  With it a
+ * chunk runs every pair with rows = target, keeps a row profile per task and brings back sub[] next to res[] */
+typedef int (*ll_sub_fn)(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                         uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream);
+typedef struct {
+	ll_sub_fn launch;
+	int excl;
+} ll_sub_t;
+int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub);
+size_t ll_pair_bytes(int qlen, int tlen, int sub);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
-int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs);
+int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs);
+int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs);      /* ksw2_host_llf.c */
 /* the stages of ksw2amd_ll_align_batch behind the two kernel passes (ksw2_host_lla.c), shared with ksw2amd_ll_align_batch_flat */
 #define LLA_FLAGS (KSW_EZ_SCORE_ONLY | KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)
 int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);

@@ -21,6 +21,16 @@ static int ll_pk_admit(int qlen, int tlen, int smax)
 	return (mn + 1) * (int64_t)smax <= 65535 && mn <= 65535;
 }
 
+/* a pair's share of a chunk's byte budget: sequences, table entries, results, the generation boundary (8 bytes per column of a task
+ * over one generation) and -- sub: rows = target whatever the lengths -- the row profile */
+size_t ll_pair_bytes(int qlen, int tlen, int sub)
+{
+	const size_t ql = (size_t)imax(qlen, 0), tl = (size_t)imax(tlen, 0);
+	const size_t rows = sub || tl >= ql ? tl : ql, cols = sub || tl >= ql ? ql : tl;
+	return rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0)
+	       + (sub ? align_up(K2A_LLSUB_BYTES(rows), 256) : 0);
+}
+
 typedef struct { int32_t rows, cols, sw; uint32_t idx; int64_t cost; } ll_sort_t;      /* sw: rows = the query (part of a packed task's shape) */
 static int cmp_shape(const void *a_, const void *b_)
 {
@@ -87,8 +97,11 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
  *     of their own.  The residue codes are checked on the device (src->check) and the result word read before any alignment kernel
  *     is launched; a code >= m ends the chunk with KSW2AMD_E_PARAM and every result at its reset value.
  * rev: the start-cell pass (beg[i] = its score, qb, tb), launched behind the forward pass on the same task table, tables, sequences
- * and results in device memory; one download brings back both arrays */
-int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg)
+ * and results in device memory; one download brings back both arrays.
+ * sb (never with rev): ksw2amd_ll_sub_batch -- rows = target for every pair, the forward launch is sb->launch, which also fills a row
+ * profile per task (behind the boundaries in the scratch, at 128 * K2aLLTask.pad) and reduces it into K2aLLSub[n] behind K2aLLRes[n] */
+int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub)
 {
 	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
@@ -99,10 +112,10 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	uint8_t *h_arena = 0, *d_arena = 0, *d_scr = 0, *d_span = 0;
 	const uint8_t *d_seq = 0;
 	K2aLLRes *h_res = 0, *d_res = 0;
-	const size_t res_bytes = (sizeof(K2aLLRes) + (rev ? sizeof(K2aLLBeg) : 0)) * (size_t)n;      /* K2aLLRes[n], then K2aLLBeg[n] */
+	const size_t res_bytes = (sizeof(K2aLLRes) + (rev ? sizeof(K2aLLBeg) : sb ? sizeof(K2aLLSub) : 0)) * (size_t)n;      /* K2aLLRes[n], then K2aLLBeg[n] or K2aLLSub[n] */
 	size_t cap_h = 0, cap_d = 0, cap_s = 0, cap_hr = 0, cap_dr = 0, cap_sp = 0;
 	int npk = 0, ni32 = 0, ntk_pk = 0, ntk = 0, nent = 0, i, rc = KSW2AMD_OK;
-	size_t tab_off, seq_off, chk_off = 0, bad_off = 0, bytes, scr = 0;
+	size_t tab_off, seq_off, chk_off = 0, bad_off = 0, bytes, scr = 0, prof = 0, prof_off = 0;
 	void *st = thread_stream();
 	if (!pk || !i32) { free(pk); free(i32); return fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); }
 	for (i = 0; i < n; ++i) {
@@ -110,10 +123,12 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		ll_sort_t s;
 		res[i].score = 0; res[i].qe = res[i].te = -1;
 		if (rev) { beg[i].score = 0; beg[i].qb = beg[i].tb = -1; }
+		if (sb) { sub[i].score2 = 0; sub[i].qe2 = sub[i].te2 = -1; }
 		if (ql <= 0 || tl <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
 		s.rows = imax(ql, tl); s.cols = imin(ql, tl); s.sw = ql > tl; s.idx = (uint32_t)i;
+		if (sb) { s.rows = tl; s.cols = ql; s.sw = 0; }          /* row maxima are per target position only if rows = target */
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
-		if (form > 0 && ll_pk_admit(ql, tl, smax)) pk[npk++] = s;
+		if (form > 0 && ll_pk_admit(ql, tl, smax) && s.cols <= 65535) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
 		else i32[ni32++] = s;
 	}
 	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
@@ -136,6 +151,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers",
 	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host");
 	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] ll-rev: pk_tasks=%d int32_tasks=%d profile=%s\n", ntk_pk, ni32, lds ? "lds" : "registers");
+	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] ll-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d\n", ntk_pk, ni32, lds ? "lds" : "registers", sb->excl);
 	if (ntk == 0 && !flat) { free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
@@ -192,8 +208,10 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 			}
 			if (!is_pk) { k->res[1] = k->res[0]; k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; }
 			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * 8, 256); }
+			if (sb) { k->pad = (int32_t)(prof / 128); prof += align_up(K2A_LLSUB_BYTES(k->nrows), 256); }
 		}
 	}
+	prof_off = scr; scr += prof;                        /* the row profiles lie behind the boundaries (a chunk stays under 3 GB: pad holds the offset) */
 	if (scr) {
 		d_scr = (uint8_t*)cache_get(BUF_TB, scr, &cap_s);
 		if (!d_scr) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: scratch allocation failed: %s", k2a_shim_last_error()); goto out; }
@@ -225,8 +243,10 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		K2aLL par;
 		par.m = m; par.smax = smax; par.oe = gapo + gape; par.ge = gape;
 		if ((!flat && k2a_shim_h2d(d_arena, h_arena, bytes, st))
-		    || k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, st)
-		    || k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, st)
+		    || (!sb && k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, st))
+		    || (!sb && k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, st))
+		    || (sb && sb->launch(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, d_scr + prof_off, sb->excl, (K2aLLSub*)(d_res + n), st))
+		    || (sb && sb->launch(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, d_scr + prof_off, sb->excl, (K2aLLSub*)(d_res + n), st))
 		    || (rev && rev(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
 		    || (rev && rev(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
 		    || k2a_shim_d2h(h_res, d_res, res_bytes, st)
@@ -239,6 +259,11 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		for (i = 0; i < npk; ++i) beg[pk[i].idx] = hb[pk[i].idx];
 		for (i = 0; i < ni32; ++i) beg[i32[i].idx] = hb[i32[i].idx];
 	}
+	if (sb) {
+		const K2aLLSub *hs = (const K2aLLSub*)(h_res + n);
+		for (i = 0; i < npk; ++i) memcpy(&sub[pk[i].idx], &hs[pk[i].idx], sizeof(K2aLLSub));       /* ksw2amd_lsub_t is K2aLLSub */
+		for (i = 0; i < ni32; ++i) memcpy(&sub[i32[i].idx], &hs[i32[i].idx], sizeof(K2aLLSub));
+	}
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);
@@ -250,12 +275,13 @@ out:
 	return rc;
 }
 
-/* ksw2amd_ll_batch (rev = 0), and the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c) */
-int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs)
+/* ksw2amd_ll_batch (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c), and ksw2amd_ll_sub_batch (ksw2_host_lls.c) */
+int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs)
 {
 	int i, rc, beg = 0, smax = -128;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
-	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs) || (sb && !subs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
 	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */
 		const ksw2amd_lpair_t *p = &pairs[i];
 		char msg[96];
@@ -272,8 +298,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 		size_t b = 0;
 		int end;
 		for (end = beg; end < n; ++end) {
-			const size_t rows = (size_t)imax(imax(pairs[end].qlen, pairs[end].tlen), 0), cols = (size_t)imax(imin(pairs[end].qlen, pairs[end].tlen), 0);
-			const size_t pb = rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0);
+			const size_t pb = ll_pair_bytes(pairs[end].qlen, pairs[end].tlen, sb != 0);
 			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
 			b += pb;
 		}
@@ -281,7 +306,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 			ll_src_t src;
 			memset(&src, 0, sizeof(src));
 			src.pairs = pairs + beg;
-			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0);
+			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0);
 		}
 		if (rc) return rc;
 		beg = end;
@@ -291,7 +316,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 
 int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
 {
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0);
 }
 
 /* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */

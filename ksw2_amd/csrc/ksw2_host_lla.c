@@ -88,7 +88,7 @@ int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
 		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
-	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_ll_rev, beg)) != KSW2AMD_OK) goto out;
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_ll_rev, beg, 0, 0)) != KSW2AMD_OK) goto out;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
 	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln);

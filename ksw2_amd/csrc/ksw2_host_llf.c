@@ -29,19 +29,21 @@ static int llf_pair_span(const ksw2amd_lflat_t *in, int i, uint64_t *lo, uint64_
 	return 1;
 }
 
-/* ksw2amd_ll_batch_flat (rev = 0), and the first two stages of ksw2amd_ll_align_batch_flat */
-static int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs)
+/* ksw2amd_ll_batch_flat (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch_flat, and ksw2amd_ll_sub_batch_flat (sb) */
+int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs)
 {
 	const size_t limit = llf_chunk_bytes();
 	int i, rc, beg = 0, smax = -128;
 	char msg[32];
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
-	if (n < 0 || !in || (n > 0 && (!in->base || !in->qoff || !in->toff || !in->qlen || !in->tlen || !res || (rev && !begs))))
+	if (n < 0 || !in || (n > 0 && (!in->base || !in->qoff || !in->toff || !in->qlen || !in->tlen || !res || (rev && !begs) || (sb && !subs))))
 		return fail(KSW2AMD_E_PARAM, "local alignment: bad flat batch arguments%s", "");
 	for (i = 0; i < n; ++i) {                              /* every argument before anything is uploaded */
 		uint64_t lo, hi;
 		res[i].score = 0; res[i].qe = res[i].te = -1;       /* a failing chunk leaves the later ones at their reset values */
 		if (rev) { begs[i].score = 0; begs[i].qb = begs[i].tb = -1; }
+		if (sb) { subs[i].score2 = 0; subs[i].qe2 = subs[i].te2 = -1; }
 		if (llf_pair_span(in, i, &lo, &hi) && (hi < lo || hi - lo > LLF_SPAN_MAX)) {
 			snprintf(msg, sizeof(msg), "%d", i);
 			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: query and target lie more than 4 GiB apart in the arena", msg);
@@ -56,8 +58,7 @@ static int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, con
 		uint64_t clo = 0, chi = 0;
 		int end, any = 0;
 		for (end = beg; end < n; ++end) {
-			const size_t rows = (size_t)imax(imax(in->qlen[end], in->tlen[end]), 0), cols = (size_t)imax(imin(in->qlen[end], in->tlen[end]), 0);
-			const size_t pb = rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + 2 * sizeof(K2aLLChk) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0);
+			const size_t pb = ll_pair_bytes(in->qlen[end], in->tlen[end], sb != 0) + 2 * sizeof(K2aLLChk);
 			uint64_t lo, hi, nlo = clo, nhi = chi;
 			if (llf_pair_span(in, end, &lo, &hi)) { nlo = any && clo < lo ? clo : lo; nhi = any && chi > hi ? chi : hi; }
 			if (end > beg && (b + pb > limit || nhi - nlo > limit || nhi - nlo > LLF_SPAN_MAX || end - beg >= (1 << 22))) break;
@@ -67,7 +68,7 @@ static int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, con
 		}
 		memset(&src, 0, sizeof(src));
 		src.flat = in; src.first = beg; src.lo = clo; src.hi = chi; src.check = k2a_shim_launch_ll_check;
-		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0);
+		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0);
 		if (rc) return rc;
 		beg = end;
 	}
@@ -76,7 +77,7 @@ static int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, con
 
 int ksw2amd_ll_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res)
 {
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0);
 }
 
 int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
@@ -94,7 +95,7 @@ int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, in
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
 	/* stages 1 and 2 on the borrowed arena */
-	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, k2a_shim_launch_ll_rev, beg)) != KSW2AMD_OK) goto reset;
+	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, k2a_shim_launch_ll_rev, beg, 0, 0)) != KSW2AMD_OK) goto reset;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
 	/* stage 3: the intervals [qoff + qb, qoff + qe] x [toff + tb, toff + te] under the scalar ksw_extz contract.  Host arena: pointers

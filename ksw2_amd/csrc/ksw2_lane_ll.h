@@ -87,7 +87,17 @@ K2A_FN void k2a_ll_key_reset(K2aLLKey &k) { k.s = 0; k.te = -1; k.qe = -1; }
  * r[rl - 1 - i] and column j holds c[cl - 1 - j].  The two halves of a packed task run over their bounding rectangle; a cell depends
  * only on cells above and to its left, so the cells outside a half's own rectangle cannot change one inside it and only have to be
  * kept out of that half's maximum: the row-maximum update carries a per-half column test, gen_end a per-half row test. */
-template<bool PK, bool LDSP, bool REV = false>
+/* 16 bytes of the row profile (ksw2amd_ll_sub_batch): four rows' maxima, or their first columns */
+#if defined(__clang__)
+typedef uint32_t k2a_ll_v4 __attribute__((ext_vector_type(4)));
+#else
+typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
+#endif
+
+/* SUB (with REV = false, rows = target): the forward pass of ksw2amd_ll_sub_batch.  Nothing changes in the
+ * recurrence; sub_store(), called next to gen_end(), writes the lane's rows of (rmax, rcol) to the task's row profile in HBM, from
+ * which k2a_ll_sub_kernel (ksw2_lane_llsub.h) takes the best row outside the window around the best cell. */
+template<bool PK, bool LDSP, bool REV = false, bool SUB = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
 	int nrows, ncols, swapped, m, lane, i0;
@@ -216,6 +226,23 @@ struct K2aLaneLL {
 				key[h].te = take ? te : key[h].te;
 				key[h].qe = take ? qe : key[h].qe;
 			}
+		}
+	}
+
+	/* SUB, end of a generation: the lane's C words of rmax, then its C words of rcol -- packed: both halves in a word, as the registers
+	 * hold them -- to bytes [8 * i0, 8 * i0 + 128) of the task's row profile `prof` (16-byte aligned), in 16-byte stores of four
+	 * consecutive registers.  A lane without a live row writes nothing: the profile ends with the last lane that has one
+	 * (K2A_LLSUB_BYTES) */
+	K2A_FN void sub_store(uint8_t *prof) const
+	{
+		if (!SUB || i0 >= nrows) return;
+		k2a_ll_v4 *p = (k2a_ll_v4*)(prof + (size_t)i0 * 8);
+#pragma unroll
+		for (int c = 0; c < C; c += 4) {
+			k2a_ll_v4 v, w;
+			v[0] = rmax[c]; v[1] = rmax[c + 1]; v[2] = rmax[c + 2]; v[3] = rmax[c + 3];
+			w[0] = rcol[c]; w[1] = rcol[c + 1]; w[2] = rcol[c + 2]; w[3] = rcol[c + 3];
+			p[c / 4] = v; p[C / 4 + c / 4] = w;
 		}
 	}
 };

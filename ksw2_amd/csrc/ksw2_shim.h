@@ -187,6 +187,12 @@ int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *t
  * ent[nent].first.  *bad, a device word the host set to K2A_LLCHK_NONE, ends up as the lowest ent[].pair with a code >= m.
  * Only ksw2_host_llf.c calls it (the simulator builds of tests/ll_util.py and tests/lla_util.py have no such symbol). */
 int k2a_shim_launch_ll_check(const K2aLLChk *ent, int nent, uint32_t nblocks, const uint8_t *seq, int m, uint32_t *bad, void *stream);
+/* ksw2amd_ll_sub_batch: the forward launch of k2a_shim_launch_ll on tasks whose rows are the target, writing
+ * every task's row profile to prof + 128 * tasks[].pad (K2A_LLSUB_BYTES(nrows) bytes, 16-byte aligned) as well, and behind it in the
+ * same stream the reduction: sub[slot] = the largest row maximum outside |t - te| <= d (d = excl, or ceil(score / smax) for excl < 0),
+ * the smallest such row, that row's first column.  Only ksw2_host_lls.c calls it (the other simulator builds have no such symbol). */
+int k2a_shim_launch_ll_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@
 #include "ksw2_lane_extfb.h"
 #include "ksw2_lane_ll.h"
 #include "ksw2_lane_llchk.h"
+#include "ksw2_lane_llsub.h"
 
 #define K2A_WPB 4          /* wavefronts per workgroup; waves never synchronise with each other */
 /* The traceback walk is a chain of dependent loads and a few dozen instructions per step on ONE lane; what it needs is many
@@ -2160,10 +2161,11 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * fres[tk.res[h]] and runs the reversed prefixes that end in that cell (limits and reversed indexing: K2aLaneLL<.., REV>); the task
  * runs over the bounding rectangle of its halves, never more generations or steps than the forward launch, and a task whose halves
  * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb. */
-template<bool PK, bool LDSP, bool REV>
+template<bool PK, bool LDSP, bool REV, bool SUB = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
-            uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+            uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg,
+            uint8_t *__restrict__ prof = nullptr)
 {
 	extern __shared__ uint8_t k2a_ll_lds[];
 	const int mm = par.m * par.m;
@@ -2177,7 +2179,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 	const uint8_t *r0 = seq + tk.roff[0], *r1 = seq + tk.roff[1 & -(int)PK];
 	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
 	uint2 *bnd = (uint2*)(scratch + tk.boff);
-	K2aLaneLL<PK, LDSP, REV> L;
+	K2aLaneLL<PK, LDSP, REV, SUB> L;
 	L.init(par, tk, lane);
 	int fq[2] = { 0, 0 }, ft[2] = { 0, 0 };        /* REV: the forward end cells */
 	if (REV) {
@@ -2235,6 +2237,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 			for (int u = 0; u < 4; ++u) { qc[u] = qn[u]; hb[u] = hn[u]; eb[u] = en[u]; }
 		}
 		L.gen_end();
+		if (SUB) L.sub_store(prof + (size_t)tk.pad * 128);
 	}
 	/* the task's best cell(s): the 64 lane keys reduced once */
 #pragma unroll
@@ -2272,6 +2275,48 @@ k2a_ll_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntas
                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	k2a_ll_task<PK, LDSP, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+/* ---------------------------------------------------------------- suboptimal score (ksw2amd_ll_sub_batch)
+ * The forward pass with SUB: the same schedule, every generation's rows of (maximum, first column) streamed to the task's row profile
+ * at prof + 128 * tk.pad.  Rows are the target for every task (the host forces the orientation). */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_fsub_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                   uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, uint8_t *__restrict__ prof)
+{
+	k2a_ll_task<PK, LDSP, false, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr, prof);
+}
+
+/* The reduction, launched behind the forward launch (the kernel boundary makes the profile and res[] visible): one wavefront per
+ * result slot -- wavefront w takes half w % nh of task w / nh; a self-paired packed task writes once.  It reads the slot's score and
+ * te, the lanes stride over the rows outside the window (ksw2_lane_llsub.h), one wavefront reduction, lane 0 writes sub[slot]. */
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ll_sub_kernel(int smax, const K2aLLTask *__restrict__ tasks, int ntasks, int pk, const K2aLLRes *__restrict__ res, const uint8_t *__restrict__ prof,
+                  int excl, K2aLLSub *__restrict__ sub)
+{
+	const int w = blockIdx.x * K2A_WPB + k2a_wave_id<true>(), nh = pk ? 2 : 1;
+	const int t = w / nh, h = w % nh;
+	if (t >= ntasks) return;
+	const int lane = threadIdx.x & 63;
+	const K2aLLTask *tk = &tasks[t];               /* only the fields needed: no copy of the task to index at run time */
+	const uint32_t slot = h ? tk->res[1] : tk->res[0];
+	if (h == 1 && slot == tk->res[0]) return;
+	const int nrows = tk->nrows;
+	const K2aLLRes r = res[slot];
+	const uint32_t *p = (const uint32_t*)(prof + (size_t)tk->pad * 128);
+	K2aLLSubKey k;
+	k2a_llsub_lane(p, pk != 0, h, nrows, r.te, k2a_llsub_window(excl, r.score, smax), lane, k);
+	for (int d = 1; d < 64; d <<= 1) {
+		const int s = __shfl_xor(k.s, d), tt = __shfl_xor(k.t, d);
+		const bool take = k2a_llsub_better(s, tt, k);
+		k.s = take ? s : k.s; k.t = take ? tt : k.t;
+	}
+	if (lane == 0) {
+		K2aLLSub o;
+		k2a_llsub_finish(p, pk != 0, h, k, o);
+		sub[slot] = o;
+	}
 }
 
 /* ---------------------------------------------------------------- residue-code check of the flat local batches (ksw2_lane_llchk.h)
@@ -2761,6 +2806,26 @@ int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *t
 	else if (pk) hipLaunchKernelGGL((k2a_ll_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else hipLaunchKernelGGL((k2a_ll_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* ksw2amd_ll_sub_batch: the forward pass that also writes the row profiles, then one reduction wavefront per result slot */
+int k2a_shim_launch_ll_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ll_fsub_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	else if (pk) hipLaunchKernelGGL((k2a_ll_fsub_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	else if (lds) hipLaunchKernelGGL((k2a_ll_fsub_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	else hipLaunchKernelGGL((k2a_ll_fsub_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	CHECK(hipGetLastError());
+	const int64_t waves = (int64_t)ntasks * (pk ? 2 : 1);
+	hipLaunchKernelGGL(k2a_ll_sub_kernel, dim3((unsigned)((waves + K2A_WPB - 1) / K2A_WPB)), block, 0, (hipStream_t)stream, par->smax, tasks, ntasks, pk, res,
+	                   (const uint8_t*)prof, excl, sub);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -195,7 +195,8 @@ typedef struct K2aLL {
 typedef struct K2aLLTask {
 	uint32_t roff[2], coff[2];       /* arena byte offsets of the row / column codes, per half (int32 tasks: [0]) */
 	uint32_t res[2];                 /* result slots of the halves; res[1] == res[0]: one alignment in both halves */
-	int32_t nrows, ncols, swapped, pad;
+	int32_t nrows, ncols, swapped;
+	int32_t pad;                     /* ksw2amd_ll_sub_batch: the task's row profile starts at byte 128 * pad of the profile (else 0) */
 	uint64_t boff;                   /* byte offset in the scratch of the generation boundary: 8 bytes per column (tasks over one generation) */
 } K2aLLTask;                         /* 48 bytes */
 typedef struct K2aLLRes {
@@ -205,6 +206,14 @@ typedef struct K2aLLRes {
 typedef struct K2aLLBeg {
 	int32_t score, qb, tb;           /* its best score (equals the forward score), qb = qe - qe', tb = te - te'; -1, -1 for a score of 0 */
 } K2aLLBeg;
+/* suboptimal score (ksw2amd_ll_sub_batch): the largest row maximum outside the rows |t - te| <= d */
+typedef struct K2aLLSub {
+	int32_t score2, qe2, te2;        /* ksw2amd_lsub_t; (0, -1, -1): no positive cell outside the window */
+} K2aLLSub;
+/* row profile of a task: 8 bytes per row (row maximum, its first column; a packed task's two halves share the words, 16 bits each),
+ * written lane by lane -- K2A_LL_C rows = 128 contiguous bytes: the maxima, then the columns -- by the lanes that own a live row */
+#define K2A_LLSUB_BYTES(nrows) ((((size_t)(nrows) + K2A_LL_C - 1) / K2A_LL_C) * (K2A_LL_C * 8))
+#define K2A_LLSUB_EXCL_MAX 0x3fffffff
 /* residue-code check of the flat local-alignment batches (ksw2amd_ll_batch_flat; ksw2_lane_llchk.h): one entry per DISTINCT sequence
  * that a chunk's pairs reference, cut into 16-byte blocks at 16-byte aligned addresses; entry [nent] is a sentinel whose first = the
  * block total */

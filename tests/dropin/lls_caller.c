@@ -1,0 +1,48 @@
+/* C caller of the suboptimal-score entries, compiled against the public header include/ksw2_amd.h and linked against libksw2_amd.
+ * Reads "m gapo gape excl", the m*m matrix, n, then per pair "qlen codes... tlen codes..." from argv[1]; prints "score qe te score2 qe2
+ * te2" per pair, once from ksw2amd_ll_sub_batch (all pairs in one call) and once from ksw2amd_ll_sub on a ksw_ll_qinit profile. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <stdint.h>
+#include "ksw2_amd.h"
+
+static uint8_t *read_seq(FILE *f, int *len)
+{
+	int i, v;
+	uint8_t *s;
+	if (fscanf(f, "%d", len) != 1) exit(2);
+	s = (uint8_t*)malloc((size_t)(*len > 0 ? *len : 1));
+	for (i = 0; i < *len; ++i) { if (fscanf(f, "%d", &v) != 1) exit(2); s[i] = (uint8_t)v; }
+	return s;
+}
+
+int main(int argc, char **argv)
+{
+	FILE *f = argc > 1 ? fopen(argv[1], "r") : 0;
+	int m, gapo, gape, excl, n, i, v;
+	int8_t *mat;
+	ksw2amd_lpair_t *pairs;
+	ksw2amd_lres_t *res;
+	ksw2amd_lsub_t *sub;
+	if (!f || fscanf(f, "%d %d %d %d", &m, &gapo, &gape, &excl) != 4) return 2;
+	mat = (int8_t*)malloc((size_t)m * m);
+	for (i = 0; i < m * m; ++i) { if (fscanf(f, "%d", &v) != 1) return 2; mat[i] = (int8_t)v; }
+	if (fscanf(f, "%d", &n) != 1) return 2;
+	pairs = (ksw2amd_lpair_t*)calloc((size_t)n + 1, sizeof(*pairs));
+	res = (ksw2amd_lres_t*)calloc((size_t)n + 1, sizeof(*res));
+	sub = (ksw2amd_lsub_t*)calloc((size_t)n + 1, sizeof(*sub));
+	for (i = 0; i < n; ++i) { pairs[i].query = read_seq(f, &pairs[i].qlen); pairs[i].target = read_seq(f, &pairs[i].tlen); }
+	if (ksw2amd_ll_sub_batch(m, mat, gapo, gape, excl, n, pairs, res, sub) != KSW2AMD_OK) { fprintf(stderr, "%s\n", ksw2amd_last_error()); return 3; }
+	for (i = 0; i < n; ++i) printf("%d %d %d %d %d %d\n", res[i].score, res[i].qe, res[i].te, sub[i].score2, sub[i].qe2, sub[i].te2);
+	for (i = 0; i < n; ++i) {
+		int qe = -2, te = -2, score;
+		ksw2amd_lsub_t s;
+		void *prof = ksw_ll_qinit(0, 2, pairs[i].qlen, pairs[i].query, m, mat);
+		if (!prof) return 3;
+		score = ksw2amd_ll_sub(prof, pairs[i].tlen, pairs[i].target, gapo, gape, excl, &qe, &te, &s);
+		free(prof);
+		printf("%d %d %d %d %d %d\n", score, qe, te, s.score2, s.qe2, s.te2);
+	}
+	fclose(f);
+	return 0;
+}

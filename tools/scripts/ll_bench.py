@@ -23,7 +23,15 @@ for the start-cell pass (its kernel: k2a_ll_rev_kernel in --kstats).  --pairs N:
 --flat host | host-pinned | device | all: ksw2amd_ll_batch_flat (with --align coords: ksw2amd_ll_align_batch_flat, KSW_EZ_SCORE_ONLY)
 from one arena, against the unchanged pointer entry on the same pairs.  On both sides the clock covers ONLY the library call: the
 ksw2amd_lpair_t array, the arena, the offset arrays, page-locking and the device copy are made before it.  --no-compare skips the
-pointer entry (a profiled run then holds 1 + reps batches of one path); --kstats adds k2a_ll_check_kernel next to k2a_ll_kernel."""
+pointer entry (a profiled run then holds 1 + reps batches of one path); --kstats adds k2a_ll_check_kernel next to k2a_ll_kernel.
+
+  python tools/scripts/ll_bench.py --workload A --sub [--excl -1] [--ktrace kernel_trace.csv] [--out profiles/lls_bench_A.json]
+
+--sub: ksw2amd_ll_sub_batch (suboptimal score) beside ksw2amd_ll_batch on the same prebuilt pair array, the
+library call alone in the clock on both sides; pairs/s and GCUPS of both and their ratio, the forms both took, how many pairs change
+orientation (qlen > tlen: ll_batch runs them with rows = query), res equality and a parity sample against tests/lls_oracle.c.
+--ktrace: the kernel_trace.csv of a `rocprofv3 --kernel-trace` run of the same command -- per batch the time of k2a_ll_kernel, of
+k2a_ll_fsub_kernel and of k2a_ll_sub_kernel, their ratio, and the batch-to-batch spread of k2a_ll_kernel over its timed batches."""
 import argparse
 import ctypes
 import csv
@@ -186,6 +194,87 @@ def main_flat(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if ok else 1
 
 
+def trace_batches(path, name, launches_per_batch):
+    """per-batch kernel time (ms) of the dispatches whose name contains `name` in a rocprofv3 kernel_trace.csv, in dispatch order"""
+    d = []
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            if name in row.get("Kernel_Name", ""):
+                d.append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6))
+    d = [x[1] for x in sorted(d)]
+    k = max(1, launches_per_batch)
+    return [sum(d[i:i + k]) for i in range(0, len(d) - k + 1, k)]
+
+
+def main_sub(a, lib, q, t, mat, gapo, gape, cells, form):
+    from tests import lls_util as ls
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res, res2, sub = (np.zeros((n, 3), dtype=np.int32) for _ in range(3))
+    rp = lambda x, ty: x.ctypes.data_as(ctypes.POINTER(ty))
+
+    def plain():
+        return L.ksw2amd_ll_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(res, ksw2_amd.LocalResult))
+
+    def withsub():
+        return L.ksw2amd_ll_sub_batch(5, mp.ctypes.data_as(i8p), gapo, gape, a.excl, n, pairs, rp(res2, ksw2_amd.LocalResult), rp(sub, ksw2_amd.LocalSub))
+
+    def timed(fn, tag):
+        os.environ["KSW2AMD_TRACE"] = "1"                      # the warm-up's form lines
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            lines = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tag in l]
+        os.environ.pop("KSW2AMD_TRACE")                        # (the binding re-reads the environment in front of every call)
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            times.append(time.perf_counter() - t0)
+        return dict(e2e_s=min(times), e2e_all_s=times, pairs_per_s=n / min(times), e2e_gcups=cells / min(times) / 1e9, forms=lines)
+
+    rec = dict(workload=a.workload, mode="sub", pairs=n, cells=cells, excl=a.excl, ll_form=form,
+               pairs_changing_orientation=int(sum(len(x) > len(y) for x, y in zip(q, t))),
+               clock="library call only: the pair array is built before it")
+    rec["ll_batch"] = timed(plain, "ll: pairs")
+    rec["ll_sub_batch"] = timed(withsub, "ll-sub:")
+    rec["sub_over_plain_e2e"] = rec["ll_sub_batch"]["e2e_s"] / rec["ll_batch"]["e2e_s"]
+    rec["res_equal"] = bool((res == res2).all())
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = ls.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, gapo, gape, a.excl)
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool((np.hstack([res2, sub])[idx] == exp).all())
+    rec["score2_positive"] = int((sub[:, 0] > 0).sum())
+    if a.ktrace:
+        # launches per batch: one per kernel form that had tasks (packed, int32), as the form lines say
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        kp = trace_batches(a.ktrace, "k2a_ll_kernel", nl(rec["ll_batch"]["forms"][0]))[1:]        # [0]: the warm-up
+        kf = trace_batches(a.ktrace, "k2a_ll_fsub_kernel", nl(rec["ll_sub_batch"]["forms"][0]))[1:]
+        kr = trace_batches(a.ktrace, "k2a_ll_sub_kernel", nl(rec["ll_sub_batch"]["forms"][0]))[1:]
+        ks = [x + y for x, y in zip(kf, kr)]
+        rec["kernel"] = dict(ll_kernel_ms=kp, fsub_kernel_ms=kf, sub_kernel_ms=kr,
+                             ll_kernel_spread=(max(kp) - min(kp)) / min(kp) if kp else None,
+                             sub_over_plain=(sum(ks) / len(ks)) / (sum(kp) / len(kp)) if kp and ks else None,
+                             note="k2a_ll_kernel of this build, same session (its code and register counts are the parent commit's)")
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["res_equal"] and rec["parity_ok"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True)
@@ -199,6 +288,9 @@ def main():
     ap.add_argument("--no-compare", action="store_true", help="with --align: skip the other path (a profiled run then holds 1 + reps batches of one path only)")
     ap.add_argument("--flat", choices=("host", "host-pinned", "device", "all"), default=None,
                     help="ksw2amd_ll_batch_flat / _align_batch_flat from one arena against the pointer entry, library calls only in the clock")
+    ap.add_argument("--sub", action="store_true", help="ksw2amd_ll_sub_batch beside ksw2amd_ll_batch on the same pair array, library calls only in the clock")
+    ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
+    ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -213,6 +305,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.sub:
+        return main_sub(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.flat:
         return main_flat(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.align:
