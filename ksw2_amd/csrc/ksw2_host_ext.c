@@ -75,7 +75,7 @@ ksw2amd_plan_t *ksw2amd_exts_plan_create(const ksw2amd_splice_t *sc, int n, cons
 		 * (tools/scripts/exts_classes.py) */
 		wn = imin(a->qlen, a->tlen) <= K2A_DM_DIAG(K2A_DM_SLOTS_S) ? 0 : imin(a->qlen, a->tlen) <= K2A_DM_DIAG(K2A_DM_SLOTS) ? 1 : 2;
 		if (ENV(EXTS_BIG)) wn = 2;        /* tests: every pair through the HBM-state kernel */
-		else if (ENV(EXTS_REG) && imin(a->qlen, a->tlen) <= K2A_DM_DIAG(K2A_DM_SLOTS)) wn = imin(wn, 1);   /* tests: 16 slots with traceback */
+		else if (ENV(EXTS_REG) && imin(a->qlen, a->tlen) <= K2A_DM_DIAG(K2A_DM_SLOTS)) wn = 1;   /* tests: 16 slots wherever the diagonal fits them */
 		if (wn == 2) {                                 /* 9 ints of state per target position, 16-byte granules */
 			d->pad = (uint32_t)(p->bnd_words / 4);
 			p->bnd_words += align_up(9 * (size_t)a->tlen, 4);

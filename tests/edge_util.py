@@ -16,7 +16,7 @@ from tests.parity_util import diff, CMP_FIELDS
 COMPAT = ka.KSW2AMD_EZ_SSE_COMPAT
 ENV_KEYS = ("KSW2AMD_NO_PK", "KSW2AMD_NO_RB", "KSW2AMD_DEFER", "KSW2AMD_SOLO", "KSW2AMD_NO_PKMP", "KSW2AMD_SIMDS", "KSW2AMD_UNIFORM",
             "KSW2AMD_STREAM_PIECE_KB", "KSW2AMD_EXTF_GRP", "KSW2AMD_EXTF_LDS", "KSW2AMD_EXTF_WIN", "KSW2AMD_EXTF_HBM", "KSW2AMD_EXTS_BIG",
-            "KSW2AMD_EXTS_REG", "KSW2AMD_TN", "KSW2AMD_PK_FIRST")
+            "KSW2AMD_EXTS_REG", "KSW2AMD_TN", "KSW2AMD_PK_FIRST", "KSW2AMD_EXTF_LANE", "KSW2AMD_EXTF_RING", "KSW2AMD_SSEC_BLK", "KSW2AMD_SSEC_HBM")
 
 
 def set_env(setenv, delenv, env):
@@ -230,14 +230,15 @@ def check_zdrop_exts(lib, setenv, delenv, seed=5, npairs=12, scale=1.0, cache=No
     mat = synth.simple_mat(5, 1, 2, 0)
     qs, ts = zdrop_pairs(seed, npairs, scale)
     n = 0
-    for env, flag in (({}, po.SPLICE_FOR), ({"KSW2AMD_EXTS_BIG": 1}, 0), ({"KSW2AMD_EXTS_REG": 1}, po.SPLICE_REV | po.SCORE_ONLY)):
+    for env, flag, forms in (({}, po.SPLICE_FOR, {"exts-win8", "exts-win16"}), ({"KSW2AMD_EXTS_BIG": 1}, 0, {"exts-hbm"}),
+                             ({"KSW2AMD_EXTS_REG": 1}, po.SPLICE_REV | po.SCORE_ONLY, {"exts-win16"})):
         set_env(setenv, delenv, env)
         run = lambda i, z: po.exts2("oracle", qs[i], ts[i], mat, 2, 1, 32, 4, zdrop=int(z), flag=flag)      # noqa: E731
         qq, tt, zs = zstar_pairs(run, qs, ts, cache, ("exts", flag, seed), need=npairs // 3)
         p = lib.make_splice_batch(qq, tt, mat, 2, 1, 32, 4, zdrop=zs, flag=flag).plan()
         kinds = {c["kernel"] for c in p.describe()}
         p.close()
-        assert kinds and all(k.startswith("exts") for k in kinds), kinds
+        assert kinds and kinds <= forms, (env, kinds)
         res = lib.exts_batch(qq, tt, mat, 2, 1, 32, 4, zdrop=zs, flag=flag)
         for i in range(len(zs)):
             exp = po.exts2("oracle", qq[i], tt[i], mat, 2, 1, 32, 4, zdrop=int(zs[i]), flag=flag)

@@ -563,7 +563,7 @@ def test_splice_aware_random_and_long(lib):
     check_exts_batch(lib, qs, ts, [None] * len(qs), mat, 2, 1, 32, 4, 0, flag, zd)
     r = lib.exts2(qs[0], ts[0], mat, 2, 1, 32, 4, flag=po.SPLICE_FOR)
     assert not diff(po.exts2("oracle", qs[0], ts[0], mat, 2, 1, 32, 4, flag=po.SPLICE_FOR), r, gu.FIELDS + ["cigar"])
-    # diagonals beyond the largest register window (1472 cells): state in HBM
+    # diagonals beyond the largest register window (960 cells): state in HBM
     big_q, big_t = [], []
     for tl in (2600, 4000, 3000):
         q, t = _intron_pair(rng, tl)

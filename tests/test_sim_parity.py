@@ -363,11 +363,17 @@ def _intron_pair(rng, tl):
 
 
 def test_sim_splice_aware_16_slots_with_traceback(sim, monkeypatch):
-    """The 16-slot register window is only chosen for score-only launches; KSW2AMD_EXTS_REG forces it with traceback."""
+    """Unforced, the 16-slot register window takes diagonals of 449 to 960 cells; KSW2AMD_EXTS_REG=1 sends every diagonal that fits 16
+    slots through it, in every mode (the form is read from the plan)."""
     monkeypatch.setenv("KSW2AMD_EXTS_REG", "1")
     rng = np.random.Generator(np.random.PCG64(31))
     for rnd in (0, 7, 14):
-        check_exts_batch(sim, *_exts_cases(rng, rnd, 950))
+        qs, ts, js, mat, q, e, q2, nc, jb, flag, zd = args = _exts_cases(rng, rnd, 950)
+        p = sim.make_splice_batch(qs, ts, mat, q, e, q2, nc, zdrop=zd, junc_bonus=jb, flag=flag, juncs=js).plan()
+        kinds = {c["kernel"] for c in p.describe()}
+        p.close()
+        assert kinds == {"exts-win16"}, (rnd, kinds)
+        check_exts_batch(sim, *args)
 
 
 def test_sim_splice_aware(sim):
