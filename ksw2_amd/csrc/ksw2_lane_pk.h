@@ -50,6 +50,7 @@
 #define KSW2_LANE_PK_H_
 
 #include "ksw2_lane.h"
+#include "ksw2_lane_rowmask.h"
 
 #define K2A_PK_STAGE(C) (3 * (C) + 4)    /* LDS words per lane group for a strip's staged rows: H, row max, arg-max; first row, bases */
 typedef uint32_t k2a_pk;                 /* { int16 lo = alignment A, int16 hi = alignment B } */
@@ -266,6 +267,53 @@ K2A_FN k2a_pk k2a_ofs_off(k2a_pk ofs) { return k2a_pk_sub(ofs, K2A_OFS); }
 struct K2aCkHead { int32_t baseA, baseB; uint32_t hd0, pad; };          /* per strip: what do_init derived from the neighbour lane */
 #define K2A_CK_STEP_BYTES 512                                            /* 64 lanes x { hin, ein } */
 
+/* Row predicates of K2aLanePk::step_rows: which of a lane's C rows are inside the band at this step -- the only use is
+ * h = live ? h : -inf.
+ * K2aRowPredLane: every lane works it out for itself (a bit mask of its live rows, one bit-field extract + one select per row):
+ * lanes that know nothing of each other -- the re-run passes, the traceback fills, the simulator.
+ * K2aRowPredUniform: the rows' lane masks as the kernel keeps them wavefront-wide (K2aRowMasks, ksw2_lane_rowmask.h): no per-lane
+ * arithmetic at all, one select per row whose condition is a scalar register pair (5.4 cycles at four wavefronts per SIMD against
+ * 6.8 for the pair: profiles/umask_valu_rate.txt). */
+struct K2aRowPredLane {
+	uint32_t live;
+	K2A_FN void begin(int dd, int w, int rows_m1)
+	{
+		/* live rows lo..hi of this strip at this column (none while the lane owns no strip: rows_m1 = -1) */
+		const int lo = k2a_max(0, dd - w);
+		const int hi = k2a_min(rows_m1, dd + w);
+		const int cnt = k2a_max(hi - lo + 1, 0);
+		live = ((1u << cnt) - 1u) << (lo & 31);                    /* lo >= 32 only with cnt = 0 */
+	}
+	K2A_FN k2a_pk pick(int c, k2a_pk h, k2a_pk neg) const { return k2a_pk_sel(k2a_bit_mask(live, c), h, neg); }
+	K2A_FN bool any() const { return live != 0; }
+};
+template<int C>
+struct K2aRowPredUniform {
+	const K2aRowMasks<C> &rm;
+	int lane;                                                      /* host builds: this lane's bit */
+	K2A_FN K2aRowPredUniform(const K2aRowMasks<C> &rm_, int lane_) : rm(rm_), lane(lane_) {}
+	K2A_FN void begin(int, int, int) {}
+	K2A_FN k2a_pk pick(int c, k2a_pk h, k2a_pk neg) const
+	{
+#if defined(__HIP_DEVICE_COMPILE__)
+		return __builtin_amdgcn_inverse_ballot_w64(rm.m[c]) ? h : neg;
+#else
+		return ((rm.m[c] >> lane) & 1u) ? h : neg;
+#endif
+	}
+	K2A_FN bool any() const
+	{
+		uint64_t a = 0;
+#pragma unroll
+		for (int c = 0; c < C; ++c) a |= rm.m[c];
+#if defined(__HIP_DEVICE_COMPILE__)
+		return __builtin_amdgcn_inverse_ballot_w64(a);
+#else
+		return ((a >> lane) & 1u) != 0;
+#endif
+	}
+};
+
 /* TN: the build for wavefront-tasks whose targets hold a wildcard code (K2aScoring.pk_tn1; the kernels look at their targets first and
  * take this build or the plain one as a whole -- a test inside the plain step costs every batch 1-3 %, 10 % at one wavefront per SIMD:
  * profiles/r6_ab_tn.txt) */
@@ -428,17 +476,21 @@ struct K2aLanePk {
 	 * Returns true when the lane computed live cells. */
 	K2A_FN bool step(const K2aScoring &sc, int k, k2a_pk hin, k2a_pk ein, k2a_pk e2in, uint32_t *tbw)
 	{
+		K2aRowPredLane rp;
+		return step_rows(sc, k, hin, ein, e2in, tbw, rp);
+	}
+
+	/* The same with the rows' band predicate handed in (K2aRowPredLane = step(); K2aRowPredUniform: k2a_fill_pk_body) */
+	template<class RowPred>
+	K2A_FN bool step_rows(const K2aScoring &sc, int k, k2a_pk hin, k2a_pk ein, k2a_pk e2in, uint32_t *tbw, RowPred &rp)
+	{
 		const int dd = k - kd;                                 /* jj - i0 */
 		const k2a_pk neg = k2a_pku(K2A_NEG16);
 		const k2a_pk gq = k2a_pk2(sc.q), ge = k2a_pk2(sc.e), gq2 = k2a_pk2(sc.q2), ge2 = k2a_pk2(sc.e2), de2 = k2a_pk2(sc.e2 - sc.e);
 		const k2a_pk bias = k2a_pk2(sc.pk_smax + sc.e);        /* largest score + row-bias step; the rows subtract their penalties from it */
 		k2a_pk e = ein, e2 = e2in;
 		if (dd >= wup) { e = neg; e2 = neg; }                  /* the cell above is outside the band */
-		/* live rows lo..hi of this strip at this column (none while the lane owns no strip: rows_m1 = -1) */
-		const int lo = k2a_max(0, dd - w);
-		const int hi = k2a_min(rows_m1, dd + w);
-		const int cnt = k2a_max(hi - lo + 1, 0);
-		const uint32_t live = ((1u << cnt) - 1u) << (lo & 31);       /* lo >= 32 only with cnt = 0 */
+		rp.begin(dd, w, rows_m1);
 		const k2a_pk jjpk = k2a_pk2(k - koff);
 		/* rows in chunks of CH: phase 1 of a chunk (its diagonal candidates, from the old H row) right before its phase 2, so only
 		 * CH candidates are alive at a time instead of C (16-18 registers: what keeps these kernels a wavefront short).  The one
@@ -479,7 +531,7 @@ struct K2aLanePk {
 					s2 = k2a_pk_sub(fc, h); h = k2a_pk_maxu(h, fc);
 					if (DUAL) { s3 = k2a_pk_sub(e2, h); h = k2a_pk_maxu(h, e2); s4 = k2a_pk_sub(f2[c], h); h = k2a_pk_maxu(h, f2[c]); }
 				}
-				h = k2a_pk_sel(k2a_bit_mask(live, c), h, neg);
+				h = rp.pick(c, h, neg);
 				/* running row maximum: ties to the last column (keep the old arg-max only where h < max), except
 				 * extz + RIGHT + CIGAR where the first column wins (take the new one only where max < h); SURVEY 8a rule 3 */
 				if (!NOMAX && DEFER) set_rmax(c, k2a_pk_maxu(rmax(c), h));       /* the column comes from k2a_argmax_kernel */
@@ -519,7 +571,7 @@ struct K2aLanePk {
 		}
 		hd0 = hin;
 		hout = hl[C - 1]; eout = e; e2out = e2;
-		return live != 0;
+		return rp.any();
 	}
 
 	/* query codes of the column this lane sees at step k+1; idle lanes read a clamped (valid, unused) column */

@@ -319,6 +319,14 @@ __device__ __forceinline__ void k2a_cptab_fill(const K2aScoring &sc, uint32_t *t
  * refreshed where strips start and end.
  * k2a_scan_codes (ksw2_lane.h, shared with the simulator): the codes >= 4 among target bytes [0, n) as seen by lane gl of a group of G:
  * bit 0 = the wildcard (4), bit 1 = a code above 4 (reported like before: K2aResult.pad[0], the host re-runs the pair). */
+/* Row masks (K2aRowMasks, ksw2_lane_rowmask.h): the score-only bodies keep the rows' band masks as wavefront-uniform lane masks in
+ * scalar registers -- one compare per step and one select per row instead of a bit-field extract and a select per row and lane.  A
+ * compile-time switch (a run-time one would double the packed score-only instantiations): -DK2A_UNIFORM_ROWMASK=0 builds the per-lane
+ * form everywhere, for A/B libraries (tools/scripts/ab_libs.sh).  The traceback bodies want "this lane computed live cells" per
+ * step and keep the per-lane form. */
+#ifndef K2A_UNIFORM_ROWMASK
+#define K2A_UNIFORM_ROWMASK 1
+#endif
 #define K2A_SYNC_WN(L) do { (L).wn = __builtin_amdgcn_ballot_w64((L).hasn != 0) != 0; } while (0)
 /* Packed-int16 resident fill: two same-shape alignments per lane group (ksw2_lane_pk.h).  k2a_fill_pk_body = one wavefront-task, in the
  * plain build or the TN one (target wildcard rows, see k2a_scan_codes); scan = what the task's look at its targets found (TN: bit 1 per
@@ -369,6 +377,9 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	L.load_query_group(0, L.knext == 0 ? L.koff_next : L.koff, L.qwA, L.qwB);
 	const size_t tbsteps = (size_t)(klast + 1);
 	uint8_t *tbp = tb + prA.tb_off;
+	constexpr bool UMASK = K2A_UNIFORM_ROWMASK != 0 && MODE == K2A_MODE_SCORE;
+	K2aRowMasks<C> RM;
+	RM.reset();
 	Stage ST;
 	if (STAGED) ST.init(&tbstage[wave * Stage::WORDS], &tbruns[wave * 64], lane, tbp + k2a_tb_word(0, gl, tbsteps, G, WB));
 	int kdone = -1;
@@ -395,7 +406,8 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 		k2a_pk e2in = DUAL ? (k2a_pk)k2a_rot1<G>((int)L.e2out) : 0u;
 
 		const bool ninit = L.need_init(k);
-		if (__builtin_amdgcn_ballot_w64(ninit) != 0) {
+		const uint64_t initmask = __builtin_amdgcn_ballot_w64(ninit);
+		if (initmask != 0) {
 			const int bsA = RB ? k2a_rot1<G>(L.baseA) : 0, bsB = RB ? k2a_rot1<G>(L.baseB) : 0;
 			if (ninit) {
 				L.do_init(sc, bsA, bsB);                          /* uses hu_prev = what arrived one step ago */
@@ -404,6 +416,19 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 			}
 			if (TN) K2A_SYNC_WN(L);
 		}
+		if (UMASK) {
+			/* a last, partial strip (rows that do not exist) or a strip at column 0 (rows 0 .. w - i0 live at once): refresh below */
+			if (initmask != 0) RM.on_init(initmask, __builtin_amdgcn_ballot_w64(ninit && L.rows_m1 != C - 1), __builtin_amdgcn_ballot_w64(ninit && L.i0 <= L.w));
+			const int dd = k - L.kd;
+			RM.advance(__builtin_amdgcn_ballot_w64((uint32_t)(dd + L.w) <= (uint32_t)(2 * L.w)));
+			if (RM.needs_refresh()) {
+				const int lo = max(0, dd - L.w), hi = min(L.rows_m1, dd + L.w);
+				uint64_t lv[C];
+#pragma unroll
+				for (int c = 0; c < C; ++c) lv[c] = __builtin_amdgcn_ballot_w64(lo <= c && c <= hi);
+				RM.refresh(lv);
+			}
+		}
 		L.hu_prev = hin;
 		if (RB) { hin = k2a_pk_add(hin, L.delta); ein = k2a_pk_add(ein, L.delta); if (DUAL) e2in = k2a_pk_add(e2in, L.delta); }
 		L.set_qb(Lane::query_pick(L.qwA, L.qwB, k & 3));      /* the codes and their column profiles (one LDS look-up per alignment) */
@@ -411,7 +436,9 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 
 		if (ckon) ckst[(size_t)k * 64] = make_uint2(hin, ein);      /* 512 contiguous bytes per wavefront and step */
 		uint32_t tw[Lane::TBWORDS];
-		const bool live = L.step(sc, k, hin, ein, e2in, tw);
+		bool live;
+		if (UMASK) { K2aRowPredUniform<C> rp(RM, lane); live = L.step_rows(sc, k, hin, ein, e2in, tw, rp); }
+		else live = L.step(sc, k, hin, ein, e2in, tw);
 		if (STAGED) { ST.put(k, tw, live); ST.step_done(k); kdone = k; }
 		else if (MODE != K2A_MODE_SCORE) {
 			if (live) {
@@ -425,6 +452,7 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 		const bool nfin = L.need_fin(k);
 		const uint64_t finmask = __builtin_amdgcn_ballot_w64(nfin);
 		if (finmask != 0) {
+			if (UMASK) RM.on_fin(finmask);                      /* end_strip(): every row of these lanes is dead from the next step on */
 			uint32_t *rowbuf = &stage_w[grp * K2A_PK_STAGE(C)];
 			if (NOMAX) {
 				if (nfin) L.fin_score_only(sc, bkA, bkB);
