@@ -368,6 +368,27 @@ int ksw2amd_ll_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int 
 int ksw2amd_ll_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int excl,
                    int *qe, int *te, ksw2amd_lsub_t *sub);
 
+/* Local alignment under the two-piece gap cost of ksw_extd (new): the four batch entries above
+ * with a gap of length l costing min(gapo + l * gape, gapo2 + l * gape2) -- the cost of the reference's scalar ksw_extd, which never swaps
+ * or orders the two pieces, and neither does this.  H(i,j) = max(0, H(i-1,j-1) + s, E, F, E2, F2) over the full matrix in exact int32
+ * arithmetic; (score, qe, te), the tie rule, the (0, -1, -1) result, qb / tb from the pass over the reversed prefixes (s' == score is
+ * checked for every pair) as for ksw2amd_ll_batch / ksw2amd_ll_align_batch.  cigar is exactly that of the scalar
+ *   ksw_extd(km, qe-qb+1, query+qb, te-tb+1, target+tb, m, mat, gapo, gape, gapo2, gape2, -1, -1, flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR), &ez)
+ * whose global score equals `score` (checked for every pair; a mismatch is an error, never returned); it begins and ends with M when
+ * min(gapo + gape, gapo2 + gape2) > 0.  With (gapo2, gape2) = (gapo, gape), or gapo2 >= gapo and gape2 >= gape, every result equals
+ * the single-piece entry's.  Arguments: m 1..127, all four gap costs 0..127, every residue code < m; flag as for
+ * ksw2amd_ll_align_batch; all checked before anything is staged or launched (flat entries: the codes on the device, chunk by chunk).
+ * One corner is rejected up front with KSW2AMD_E_PARAM: the two align entries with m = 1, whatever the flag (the scalar ksw_extd aligns
+ * nothing when m <= 1, so there is no CIGAR contract to meet; ksw2amd_lld_batch / _flat accept m = 1).  The flat entries carry the chunking,
+ * the on-device code check, the reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat /
+ * ksw2amd_ll_align_batch_flat unchanged.  Device failures: a negative code, no CPU fallback.  KSW2AMD_LL_FORM / KSW2AMD_LL_CHUNK_BYTES
+ * govern these entries too; KSW2AMD_LL_LDS only their int32 tasks (packed two-piece tasks always read scores from LDS).
+ * Not offered: a two-piece suboptimal score, single-pair entries on a ksw_ll_qinit profile. */
+int ksw2amd_lld_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
+int ksw2amd_lld_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+int ksw2amd_lld_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
+int ksw2amd_lld_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
+
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t
  * or NULL), fetch = wait + download + fill ez[]. */

@@ -111,7 +111,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_set_small_call_cells", "ksw2amd_small_call_count", "ksw2amd_stream_stats", "ksw2amd_host_phase_us", "ksw2amd_exts_batch_device", "ksw2amd_extf_batch_device",
            "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align",
            "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
-           "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub"]
+           "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
+           "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -120,7 +121,8 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_sse_plan_create", "ksw2amd_exts_plan_create", "ksw2amd_extf_plan_create", "ksw2amd_plan_run",
                 "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
                 "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
-                "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub"]
+                "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
+                "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -260,6 +262,11 @@ class Library:
         if hasattr(L, "ksw2amd_ll_batch_flat"):     # (nor the flat entries and their check kernel's twin: tests/llf_util.py adds them)
             L.ksw2amd_ll_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
             L.ksw2amd_ll_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_lld_batch"):         # (nor the two-piece entries and their kernels' twin: tests/lld_util.py adds them)
+            L.ksw2amd_lld_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_lld_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_lld_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_lld_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -567,6 +574,59 @@ class Library:
         d = self._aln_to_dict(a)
         assert d["score"] == int(score)
         return d
+
+    # ---- local alignment under the two-piece gap cost of ksw_extd: min(gapo + l * gape, gapo2 + l * gape2) for a gap of length l
+    def lld_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, m=None, pairs=None, n=None):
+        """ksw2amd_lld_batch: ll_batch under the two-piece gap cost -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_lld_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, n, pairs,
+                                        out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def lld_align_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, flag=0, m=None, pairs=None, n=None):
+        """ksw2amd_lld_align_batch(km=NULL, ...): ll_align_batch under the two-piece gap cost (the CIGAR is the scalar ksw_extd's)."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        aln = (LocalAln * max(n, 1))()
+        rc = self.lib.ksw2amd_lld_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, flag, n, pairs, aln)
+        out = [self._aln_to_dict(aln[i]) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def lld_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, m=None, device_base=None, out=None):
+        """ksw2amd_lld_batch_flat: lld_batch on an arena (see ll_batch_flat) -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1] == 3
+        rc = self.lib.ksw2amd_lld_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, n, ctypes.byref(f),
+                                             out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def lld_align_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, flag=0, m=None, device_base=None, aln=None):
+        """ksw2amd_lld_align_batch_flat(km=NULL, ...): lld_align_batch on an arena (see ll_align_batch_flat) -> list of dicts."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_lld_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, flag, n, ctypes.byref(f), aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

@@ -312,18 +312,35 @@ typedef struct {
 	ll_sub_fn launch;
 	int excl;
 } ll_sub_t;
+/* two-piece gap cost (ksw2_host_lld.c).  fwd = k2a_shim_launch_lld, passed in the same way (the start-cell
+ * launch k2a_shim_launch_lld_rev travels as the ll_rev_fn): only ksw2_host_lld.o names the two.  With it a chunk scores gaps with
+ * min(gapo + l * gape, gapo2 + l * gape2), launches fwd for the forward pass and keeps 16 bytes per column of generation boundary.
+ * Never together with an ll_sub_t */
+typedef int (*ll_fwd_fn)(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                         uint8_t *scratch, K2aLLRes *res, void *stream);
+typedef struct {
+	int gapo2, gape2;
+	ll_fwd_fn fwd;
+	int pk_reg;                        /* 1: the packed kernels have a register-profile form (0: packed tasks take the LDS profile; trace line only) */
+} ll_dual_t;
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
-             const ll_sub_t *sb, ksw2amd_lsub_t *sub);
-size_t ll_pair_bytes(int qlen, int tlen, int sub);
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du);
+size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                const ll_sub_t *sb, ksw2amd_lsub_t *subs);
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du);
 int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                 const ll_sub_t *sb, ksw2amd_lsub_t *subs);      /* ksw2_host_llf.c */
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du);      /* ksw2_host_llf.c */
 /* the stages of ksw2amd_ll_align_batch behind the two kernel passes (ksw2_host_lla.c), shared with ksw2amd_ll_align_batch_flat */
 #define LLA_FLAGS (KSW_EZ_SCORE_ONLY | KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)
 int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);
-int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln);
+int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln,
+               const ll_dual_t *du);      /* du: the scalar ksw_extd with (gapo2, gape2) instead of ksw_extz */
+/* ksw2amd_ll_align_batch / ksw2amd_ll_align_batch_flat with the start-cell launch (and the two-piece cost) as parameters */
+int lla_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln, ll_rev_fn rev,
+                 const ll_dual_t *du);
+int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln, ll_rev_fn rev,
+                 const ll_dual_t *du);
 #pragma GCC visibility pop
 #endif

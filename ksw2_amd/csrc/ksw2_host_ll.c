@@ -9,6 +9,7 @@
  * This is the only host object that calls k2a_shim_launch_ll (tests/sim links the other four against a simulator without it).
  * ksw2amd_ll_align_batch (ksw2_host_lla.c) runs its start-cell pass from what a chunk staged here: it hands ll_batch_ex the launch as a
  * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
+ * The two-piece entries (ksw2_host_lld.c) hand in their forward and start-cell launches and the second gap pair the same way (ll_dual_t).
  */
 #include "ksw2_host_int.h"
 
@@ -22,12 +23,12 @@ static int ll_pk_admit(int qlen, int tlen, int smax)
 }
 
 /* a pair's share of a chunk's byte budget: sequences, table entries, results, the generation boundary (8 bytes per column of a task
- * over one generation) and -- sub: rows = target whatever the lengths -- the row profile */
-size_t ll_pair_bytes(int qlen, int tlen, int sub)
+ * over one generation; dual: 16) and -- sub: rows = target whatever the lengths -- the row profile */
+size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual)
 {
 	const size_t ql = (size_t)imax(qlen, 0), tl = (size_t)imax(tlen, 0);
 	const size_t rows = sub || tl >= ql ? tl : ql, cols = sub || tl >= ql ? ql : tl;
-	return rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * 8, 256) : 0)
+	return rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * (dual ? 16 : 8), 256) : 0)
 	       + (sub ? align_up(K2A_LLSUB_BYTES(rows), 256) : 0);
 }
 
@@ -99,13 +100,17 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
  * rev: the start-cell pass (beg[i] = its score, qb, tb), launched behind the forward pass on the same task table, tables, sequences
  * and results in device memory; one download brings back both arrays.
  * sb (never with rev): ksw2amd_ll_sub_batch -- rows = target for every pair, the forward launch is sb->launch, which also fills a row
- * profile per task (behind the boundaries in the scratch, at 128 * K2aLLTask.pad) and reduces it into K2aLLSub[n] behind K2aLLRes[n] */
+ * profile per task (behind the boundaries in the scratch, at 128 * K2aLLTask.pad) and reduces it into K2aLLSub[n] behind K2aLLRes[n]
+ * du (never with sb): the two-piece gap cost of ksw2amd_lld_batch -- the forward launch is du->fwd (rev: the caller's two-piece start-cell
+ * launch), the boundary holds 16 bytes per column */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
-             const ll_sub_t *sb, ksw2amd_lsub_t *sub)
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du)
 {
 	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
+	const ll_fwd_fn fwd = du ? du->fwd : k2a_shim_launch_ll;
+	const char *tn = du ? "lld" : "ll";                  /* the trace lines' prefix */
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
@@ -148,9 +153,10 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	qsort(pk, (size_t)ntk_pk, 2 * sizeof(ll_sort_t), cmp_cost);        /* tasks (pairs of entries) longest first */
 	qsort(i32, (size_t)ni32, sizeof(ll_sort_t), cmp_cost);
 	ntk = ntk_pk + ni32;
-	if (trace_on()) fprintf(stderr, "[ksw2_amd] ll: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s\n", n, ntk_pk, ni32, lds ? "lds" : "registers",
-	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host");
-	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] ll-rev: pk_tasks=%d int32_tasks=%d profile=%s\n", ntk_pk, ni32, lds ? "lds" : "registers");
+	if (trace_on()) fprintf(stderr, "[ksw2_amd] %s: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s%s\n", tn, n, ntk_pk, ni32, lds ? "lds" : "registers",
+	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host", du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
+	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] %s-rev: pk_tasks=%d int32_tasks=%d profile=%s%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers",
+	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] ll-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d\n", ntk_pk, ni32, lds ? "lds" : "registers", sb->excl);
 	if (ntk == 0 && !flat) { free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
@@ -207,7 +213,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 				}
 			}
 			if (!is_pk) { k->res[1] = k->res[0]; k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; }
-			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * 8, 256); }
+			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * (du ? 16 : 8), 256); }
 			if (sb) { k->pad = (int32_t)(prof / 128); prof += align_up(K2A_LLSUB_BYTES(k->nrows), 256); }
 		}
 	}
@@ -242,9 +248,10 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	{
 		K2aLL par;
 		par.m = m; par.smax = smax; par.oe = gapo + gape; par.ge = gape;
+		par.oe2 = du ? du->gapo2 + du->gape2 : 0; par.ge2 = du ? du->gape2 : 0;
 		if ((!flat && k2a_shim_h2d(d_arena, h_arena, bytes, st))
-		    || (!sb && k2a_shim_launch_ll(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, st))
-		    || (!sb && k2a_shim_launch_ll(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, st))
+		    || (!sb && fwd(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, st))
+		    || (!sb && fwd(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, st))
 		    || (sb && sb->launch(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, d_scr + prof_off, sb->excl, (K2aLLSub*)(d_res + n), st))
 		    || (sb && sb->launch(0, lds, &par, (const K2aLLTask*)d_arena + ntk_pk, ni32, d_seq, d_arena + tab_off, d_scr, d_res, d_scr + prof_off, sb->excl, (K2aLLSub*)(d_res + n), st))
 		    || (rev && rev(1, lds, &par, (const K2aLLTask*)d_arena, ntk_pk, d_seq, d_arena + tab_off, d_scr, d_res, (K2aLLBeg*)(d_res + n), st))
@@ -277,10 +284,10 @@ out:
 
 /* ksw2amd_ll_batch (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c), and ksw2amd_ll_sub_batch (ksw2_host_lls.c) */
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                const ll_sub_t *sb, ksw2amd_lsub_t *subs)
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
 {
 	int i, rc, beg = 0, smax = -128;
-	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
+	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs) || (sb && !subs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
 	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */
 		const ksw2amd_lpair_t *p = &pairs[i];
@@ -298,7 +305,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 		size_t b = 0;
 		int end;
 		for (end = beg; end < n; ++end) {
-			const size_t pb = ll_pair_bytes(pairs[end].qlen, pairs[end].tlen, sb != 0);
+			const size_t pb = ll_pair_bytes(pairs[end].qlen, pairs[end].tlen, sb != 0, du != 0);
 			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
 			b += pb;
 		}
@@ -306,7 +313,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 			ll_src_t src;
 			memset(&src, 0, sizeof(src));
 			src.pairs = pairs + beg;
-			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0);
+			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du);
 		}
 		if (rc) return rc;
 		beg = end;
@@ -316,7 +323,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 
 int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
 {
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, 0);
 }
 
 /* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */

@@ -37,7 +37,8 @@ int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_lal
 /* stage 3 for the na pairs of aln[] with a positive score: the sub-ranges as extension pairs into HOST memory; the caller's CIGAR
  * buffers travel through ez[] and back.  at_start = 0: pairs[i] are the full sequences; 1: pairs[i].query / .target already point at
  * residues qb / tb (ksw2_host_llf.c: the intervals of a device arena, brought back) */
-int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln)
+int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln,
+               const ll_dual_t *du)
 {
 	ksw2amd_pair_t *pp = (ksw2amd_pair_t*)malloc(sizeof(*pp) * (size_t)na);
 	ksw_extz_t *ez = (ksw_extz_t*)calloc((size_t)na, sizeof(*ez));
@@ -57,8 +58,8 @@ int lla_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag,
 	}
 	{
 		ksw2amd_scoring_t sc;
-		sc.m = m; sc.mat = mat; sc.q = (int8_t)gapo; sc.e = (int8_t)gape; sc.q2 = 0; sc.e2 = 0;
-		rc = ext_batch_scalar(0, km, &sc, na, pp, ez);
+		sc.m = m; sc.mat = mat; sc.q = (int8_t)gapo; sc.e = (int8_t)gape; sc.q2 = (int8_t)(du ? du->gapo2 : 0); sc.e2 = (int8_t)(du ? du->gape2 : 0);
+		rc = ext_batch_scalar(du != 0, km, &sc, na, pp, ez);      /* du: the scalar ksw_extd, the pieces in the caller's order */
 	}
 	for (k = 0; k < na; ++k) {                 /* the buffers may have grown or moved: always hand them back */
 		ksw2amd_laln_t *a = &aln[idx[k]];
@@ -75,7 +76,8 @@ out:
 	return rc;
 }
 
-int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+int lla_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln, ll_rev_fn rev,
+                 const ll_dual_t *du)
 {
 	ksw2amd_lres_t *res = 0;
 	K2aLLBeg *beg = 0;
@@ -88,13 +90,18 @@ int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
 		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
-	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_ll_rev, beg, 0, 0)) != KSW2AMD_OK) goto out;
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, rev, beg, 0, 0, du)) != KSW2AMD_OK) goto out;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
-	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln);
+	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln, du);
 out:
 	free(res); free(beg);
 	return rc;
+}
+
+int ksw2amd_ll_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+{
+	return lla_align_ex(km, m, mat, gapo, gape, flag, n, pairs, aln, k2a_shim_launch_ll_rev, 0);
 }
 
 int ksw2amd_ll_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln)

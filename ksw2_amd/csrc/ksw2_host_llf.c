@@ -31,12 +31,12 @@ static int llf_pair_span(const ksw2amd_lflat_t *in, int i, uint64_t *lo, uint64_
 
 /* ksw2amd_ll_batch_flat (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch_flat, and ksw2amd_ll_sub_batch_flat (sb) */
 int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                 const ll_sub_t *sb, ksw2amd_lsub_t *subs)
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
 {
 	const size_t limit = llf_chunk_bytes();
 	int i, rc, beg = 0, smax = -128;
 	char msg[32];
-	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK) return rc;
+	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || !in || (n > 0 && (!in->base || !in->qoff || !in->toff || !in->qlen || !in->tlen || !res || (rev && !begs) || (sb && !subs))))
 		return fail(KSW2AMD_E_PARAM, "local alignment: bad flat batch arguments%s", "");
 	for (i = 0; i < n; ++i) {                              /* every argument before anything is uploaded */
@@ -58,7 +58,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 		uint64_t clo = 0, chi = 0;
 		int end, any = 0;
 		for (end = beg; end < n; ++end) {
-			const size_t pb = ll_pair_bytes(in->qlen[end], in->tlen[end], sb != 0) + 2 * sizeof(K2aLLChk);
+			const size_t pb = ll_pair_bytes(in->qlen[end], in->tlen[end], sb != 0, du != 0) + 2 * sizeof(K2aLLChk);
 			uint64_t lo, hi, nlo = clo, nhi = chi;
 			if (llf_pair_span(in, end, &lo, &hi)) { nlo = any && clo < lo ? clo : lo; nhi = any && chi > hi ? chi : hi; }
 			if (end > beg && (b + pb > limit || nhi - nlo > limit || nhi - nlo > LLF_SPAN_MAX || end - beg >= (1 << 22))) break;
@@ -68,7 +68,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 		}
 		memset(&src, 0, sizeof(src));
 		src.flat = in; src.first = beg; src.lo = clo; src.hi = chi; src.check = k2a_shim_launch_ll_check;
-		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0);
+		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du);
 		if (rc) return rc;
 		beg = end;
 	}
@@ -77,10 +77,11 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 
 int ksw2amd_ll_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res)
 {
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, 0);
 }
 
-int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
+int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln, ll_rev_fn rev,
+                 const ll_dual_t *du)
 {
 	ksw2amd_lres_t *res = 0;
 	K2aLLBeg *beg = 0;
@@ -95,10 +96,10 @@ int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, in
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
 	/* stages 1 and 2 on the borrowed arena */
-	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, k2a_shim_launch_ll_rev, beg, 0, 0)) != KSW2AMD_OK) goto reset;
+	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, rev, beg, 0, 0, du)) != KSW2AMD_OK) goto reset;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
-	/* stage 3: the intervals [qoff + qb, qoff + qe] x [toff + tb, toff + te] under the scalar ksw_extz contract.  Host arena: pointers
+	/* stage 3: the intervals [qoff + qb, qoff + qe] x [toff + tb, toff + te] under the scalar ksw_extz (du: ksw_extd) contract.  Host arena: pointers
 	 * into it.  Device arena: the span of the intervals comes back in one copy, then the same pointer path */
 	pp = (ksw2amd_lpair_t*)malloc(sizeof(*pp) * (size_t)n);
 	if (!pp) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
@@ -124,11 +125,16 @@ int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, in
 		}
 	} else
 		for (i = 0; i < n; ++i) { pp[i].query = in->base + in->qoff[i]; pp[i].target = in->base + in->toff[i]; pp[i].qlen = in->qlen[i]; pp[i].tlen = in->tlen[i]; }
-	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pp, in->on_device != 0, na, aln);
+	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pp, in->on_device != 0, na, aln, du);
 	goto out;
 reset:
 	for (i = 0; aln && i < n; ++i) { aln[i].score = 0; aln[i].qb = aln[i].qe = aln[i].tb = aln[i].te = -1; aln[i].n_cigar = 0; }
 out:
 	free(res); free(beg); free(pp); free(host);
 	return rc;
+}
+
+int ksw2amd_ll_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
+{
+	return llf_align_ex(km, m, mat, gapo, gape, flag, n, in, aln, k2a_shim_launch_ll_rev, 0);
 }

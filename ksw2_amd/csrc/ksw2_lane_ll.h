@@ -16,7 +16,7 @@
  * Schedule (the strip schedule of ksw2_lane.h without a band): rows are the longer sequence, cut into generations of 64 strips of
  * C rows; lane l owns strip l of a generation and walks the columns one per step, skewed by l steps, so the bottom row's (H, E) of
  * strip l reaches lane l + 1 by one DPP rotate per value and step.  Lane 63's bottom row goes to a per-task boundary in HBM
- * (8 bytes per column) that lane 0 reads in the next generation.  Generations run one after the other: 63 idle lane-steps per
+ * (8 bytes per column; DUAL: 16, H, E, E2 and a pad word moved as one access) that lane 0 reads in the next generation.  Generations run one after the other: 63 idle lane-steps per
  * generation and lane, and every lane changes strips at the same step.
  *
  * Maximum: every row keeps its largest H and the first column that reached it (strict >, columns ascending); at the end of a
@@ -97,13 +97,19 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
 /* SUB (with REV = false, rows = target): the forward pass of ksw2amd_ll_sub_batch.  Nothing changes in the
  * recurrence; sub_store(), called next to gen_end(), writes the lane's rows of (rmax, rcol) to the task's row profile in HBM, from
  * which k2a_ll_sub_kernel (ksw2_lane_llsub.h) takes the best row outside the window around the best cell. */
-template<bool PK, bool LDSP, bool REV = false, bool SUB = false>
+/* DUAL: the two-piece gap cost of ksw2amd_lld_batch, min(gapo + l * gape, gapo2 + l * gape2) for a gap of
+ * length l: a second pair of gap states E2 / F2 under (oe2, ge2) beside E / F, clamped at 0 like them (max(0, .., max(X, 0)) = max(0, .., X),
+ * and max(H - oe, max(X, 0) - ge, 0) = max(max(H - oe, X - ge), 0) because -ge <= 0: H never sees the clamp), f2[] per row and
+ * an e2 chain down the strip that reaches the lane below (and the boundary) with H and E.  With DUAL = false nothing of it exists. */
+template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
 	int nrows, ncols, swapped, m, lane, i0;
 	uint32_t smax, oe, ge;                     /* packed: the value in both halves */
+	uint32_t oe2, ge2;                         /* DUAL: the second piece */
 	uint32_t hu_prev;                          /* H(i0 - 1, jj - 1): what the lane above delivered one step earlier */
 	uint32_t hl[C], f[C], rmax[C], rcol[C];    /* H(i, jj - 1), F(i, jj), row maximum and its first column */
+	uint32_t f2[DUAL ? C : 1];                 /* DUAL: F2(i, jj) */
 	uint32_t pa[C], pb[PK ? C : 1], pw[LDSP ? 1 : C];   /* register profile: pen bytes for column codes 0..3 (pa: low half, pb: high
 	                                                     * half), pw: code 4; LDS profile: pa / pb = row code * m */
 	K2aLLKey key[NH];
@@ -124,6 +130,7 @@ struct K2aLaneLL {
 		nrows = tk.nrows; ncols = tk.ncols; swapped = tk.swapped; m = par.m; lane = lane_;
 		const uint32_t x = PK ? 0x10001u : 1u;
 		smax = (uint32_t)par.smax * x; oe = (uint32_t)par.oe * x; ge = (uint32_t)par.ge * x;
+		if (DUAL) { oe2 = (uint32_t)par.oe2 * x; ge2 = (uint32_t)par.ge2 * x; }
 		for (int h = 0; h < NH; ++h) k2a_ll_key_reset(key[h]);
 	}
 
@@ -143,6 +150,7 @@ struct K2aLaneLL {
 				a = i < nrows ? r0[i] : 0u; b = (PK && i < nrows) ? r1[i] : 0u;
 			}
 			hl[c] = 0; f[c] = 0; rmax[c] = 0; rcol[c] = 0;
+			if (DUAL) f2[DUAL ? c : 0] = 0;
 			if (LDSP) {
 				pa[c] = a * (uint32_t)m;
 				if (PK) pb[c] = b * (uint32_t)m;
@@ -164,7 +172,14 @@ struct K2aLaneLL {
 	 * qc: column code (packed: low byte for the low half, next byte for the high half); hout / eout: the same for the lane below */
 	K2A_FN void step(int jj, uint32_t hin, uint32_t ein, uint32_t qc, const uint8_t *tab, uint32_t &hout, uint32_t &eout)
 	{
-		uint32_t hd = hu_prev, e = ein;
+		uint32_t e2out;
+		step(jj, hin, ein, 0u, qc, tab, hout, eout, e2out);
+	}
+
+	/* the same with the second piece's chain: e2in = E2(i0, jj) from the lane above, e2out for the lane below (DUAL = false: unused) */
+	K2A_FN void step(int jj, uint32_t hin, uint32_t ein, uint32_t e2in, uint32_t qc, const uint8_t *tab, uint32_t &hout, uint32_t &eout, uint32_t &e2out)
+	{
+		uint32_t hd = hu_prev, e = ein, e2 = e2in;
 		hu_prev = hin;
 		uint32_t sel = 0, wmask = 0, q0 = qc & 0xffu, q1 = (qc >> 8) & 0xffu;
 		if (!LDSP) {
@@ -185,9 +200,15 @@ struct K2aLaneLL {
 			uint32_t h;
 			if (PK) {
 				h = k2a_ll_max(k2a_ll_max(k2a_ll_subs(k2a_ll_adds(hd, smax), pen), e), f[c]);
+				if (DUAL) h = k2a_ll_max(k2a_ll_max(h, e2), f2[DUAL ? c : 0]);
 				const uint32_t hoe = k2a_ll_subs(h, oe);
 				e = k2a_ll_max(hoe, k2a_ll_subs(e, ge));
 				f[c] = k2a_ll_max(hoe, k2a_ll_subs(f[c], ge));
+				if (DUAL) {
+					const uint32_t hoe2 = k2a_ll_subs(h, oe2);
+					e2 = k2a_ll_max(hoe2, k2a_ll_subs(e2, ge2));
+					f2[DUAL ? c : 0] = k2a_ll_max(hoe2, k2a_ll_subs(f2[DUAL ? c : 0], ge2));
+				}
 				const uint32_t hm = (REV && PK) ? h & cmask : h;                      /* REV: 0 in a half whose rectangle ends before jj */
 				const uint32_t d = k2a_ll_subs(hm, rmax[c]);                          /* > 0 in a half where h is a new row maximum */
 				const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
@@ -195,10 +216,16 @@ struct K2aLaneLL {
 				rcol[c] = (jj2 & mask) | (rcol[c] & ~mask);
 			} else {
 				const int t = (int)hd + (int)smax - (int)pen;                          /* e, f >= 0: h >= 0 without a clamp */
-				const int hi = k2a_max(k2a_max(t, (int)e), (int)f[c]);
+				int hi = k2a_max(k2a_max(t, (int)e), (int)f[c]);
+				if (DUAL) hi = k2a_max3(hi, (int)e2, (int)f2[DUAL ? c : 0]);
 				const int hoe = hi - (int)oe;
 				e = (uint32_t)k2a_max3(hoe, (int)e - (int)ge, 0);
 				f[c] = (uint32_t)k2a_max3(hoe, (int)f[c] - (int)ge, 0);
+				if (DUAL) {
+					const int hoe2 = hi - (int)oe2;
+					e2 = (uint32_t)k2a_max3(hoe2, (int)e2 - (int)ge2, 0);
+					f2[DUAL ? c : 0] = (uint32_t)k2a_max3(hoe2, (int)f2[DUAL ? c : 0] - (int)ge2, 0);
+				}
 				h = (uint32_t)hi;
 				if (hi > (int)rmax[c]) { rmax[c] = h; rcol[c] = jj2; }
 			}
@@ -207,6 +234,7 @@ struct K2aLaneLL {
 		}
 		hout = hl[C - 1];
 		eout = e;
+		e2out = e2;
 	}
 
 	/* end of a generation: fold the live rows into the lane's key(s).  Every row is looked at (no early exit: the rows past the

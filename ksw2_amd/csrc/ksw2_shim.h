@@ -182,6 +182,13 @@ int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
  * Only ksw2_host_lla.c calls it (the simulator builds of tests/ll_util.py link the other host objects without it). */
 int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+/* The same two launches under the two-piece gap cost of ksw2amd_lld_batch (par->oe2 / ge2): tasks over K2A_LL_ROWS
+ * rows keep 16 bytes per column at scratch + tasks[].boff (16-byte aligned).  Packed tasks take the LDS profile whatever `lds` says
+ * unless K2A_LLD_PK_REG.  Only ksw2_host_lld.c calls them (the other simulator builds have no such symbols). */
+int k2a_shim_launch_lld(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream);
+int k2a_shim_launch_lld_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
 /* Residue-code check of the flat local-alignment batches (ksw2_lane_llchk.h), launched in `stream` before the chunk's alignment
  * kernels: ent[nent + 1] lists the chunk's distinct sequences (offsets into seq) and numbers their 16-byte blocks, nblocks =
  * ent[nent].first.  *bad, a device word the host set to K2A_LLCHK_NONE, ends up as the lowest ent[].pair with a code >= m.

@@ -2188,8 +2188,10 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * REV (k2a_ll_rev_kernel): the start-cell pass of ksw2amd_ll_align_batch over the same task table.  Half h reads its forward result
  * fres[tk.res[h]] and runs the reversed prefixes that end in that cell (limits and reversed indexing: K2aLaneLL<.., REV>); the task
  * runs over the bounding rectangle of its halves, never more generations or steps than the forward launch, and a task whose halves
- * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb. */
-template<bool PK, bool LDSP, bool REV, bool SUB = false>
+ * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb.
+ * DUAL (k2a_lld_kernel / k2a_lld_rev_kernel): the two-piece gap cost.  E2 travels with H and E: one more rotate
+ * per step, and a boundary entry of 16 bytes per column (H, E, E2, pad) stored and prefetched as one access. */
+template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
             uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg,
@@ -2207,7 +2209,8 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 	const uint8_t *r0 = seq + tk.roff[0], *r1 = seq + tk.roff[1 & -(int)PK];
 	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
 	uint2 *bnd = (uint2*)(scratch + tk.boff);
-	K2aLaneLL<PK, LDSP, REV, SUB> L;
+	uint4 *bnd2 = (uint4*)(scratch + tk.boff);        /* DUAL: the host sized and aligned the boundary for 16 bytes per column */
+	K2aLaneLL<PK, LDSP, REV, SUB, DUAL> L;
 	L.init(par, tk, lane);
 	int fq[2] = { 0, 0 }, ft[2] = { 0, 0 };        /* REV: the forward end cells */
 	if (REV) {
@@ -2233,36 +2236,46 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 		}
 		L.gen_begin(g, r0, r1, ltab);
 		/* inputs of step k: column code(s) of jj = k - lane (clamped into the sequence), lane 0's boundary entry of column k */
-		uint32_t qc[4], hb[4], eb[4];
-		auto fetch = [&](int k, uint32_t &q, uint32_t &h, uint32_t &e) {
+		uint32_t qc[4], hb[4], eb[4], e2b[DUAL ? 4 : 1];
+		auto fetch = [&](int k, uint32_t &q, uint32_t &h, uint32_t &e, uint32_t &e2) {
 			const int jj = k2a_min(k2a_max(k - lane, 0), ncols - 1);
 			if (REV) {                                 /* column jj of a half is c[cl - 1 - jj]; past its limit: its first byte */
 				const int j0 = k2a_max(cl0 - 1 - jj, 0), j1 = k2a_max(cl1 - 1 - jj, 0);
 				q = PK ? (uint32_t)c0[j0] | ((uint32_t)c1[j1] << 8) : (uint32_t)c0[j0];
 			} else q = PK ? (uint32_t)c0[jj] | ((uint32_t)c1[jj] << 8) : (uint32_t)c0[jj];
-			h = e = 0;
-			if (lane == 0 && from_bnd) { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
+			h = e = e2 = 0;
+			if (lane == 0 && from_bnd) {
+				if (DUAL) { const uint4 v = bnd2[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; e2 = v.z; }
+				else { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
+			}
 		};
+		uint32_t unused2 = 0;
 #pragma unroll
-		for (int u = 0; u < 4; ++u) fetch(u, qc[u], hb[u], eb[u]);
-		uint32_t hin = 0, ein = 0;
+		for (int u = 0; u < 4; ++u) fetch(u, qc[u], hb[u], eb[u], DUAL ? e2b[DUAL ? u : 0] : unused2);
+		uint32_t hin = 0, ein = 0, e2in = 0;
 		for (int k0 = 0; k0 < nsteps; k0 += 4) {
-			uint32_t qn[4], hn[4], en[4];
+			uint32_t qn[4], hn[4], en[4], e2n[DUAL ? 4 : 1];
 #pragma unroll
-			for (int u = 0; u < 4; ++u) fetch(k0 + 4 + u, qn[u], hn[u], en[u]);
+			for (int u = 0; u < 4; ++u) fetch(k0 + 4 + u, qn[u], hn[u], en[u], DUAL ? e2n[DUAL ? u : 0] : unused2);
 #pragma unroll
 			for (int u = 0; u < 4; ++u) {
 				const int jj = k0 + u - lane;
-				uint32_t ho = 0, eo = 0;
+				uint32_t ho = 0, eo = 0, e2o = 0;
 				if ((unsigned)jj < (unsigned)ncols) {
-					L.step(jj, lane == 0 ? hb[u] : hin, lane == 0 ? eb[u] : ein, qc[u], ltab, ho, eo);
-					if (to_bnd && lane == 63) bnd[jj] = make_uint2(ho, eo);
+					if (DUAL) {
+						L.step(jj, lane == 0 ? hb[u] : hin, lane == 0 ? eb[u] : ein, lane == 0 ? e2b[DUAL ? u : 0] : e2in, qc[u], ltab, ho, eo, e2o);
+						if (to_bnd && lane == 63) bnd2[jj] = make_uint4(ho, eo, e2o, 0u);
+					} else {
+						L.step(jj, lane == 0 ? hb[u] : hin, lane == 0 ? eb[u] : ein, qc[u], ltab, ho, eo);
+						if (to_bnd && lane == 63) bnd[jj] = make_uint2(ho, eo);
+					}
 				}
 				hin = (uint32_t)k2a_rot1<64>((int)ho);
 				ein = (uint32_t)k2a_rot1<64>((int)eo);
+				if (DUAL) e2in = (uint32_t)k2a_rot1<64>((int)e2o);
 			}
 #pragma unroll
-			for (int u = 0; u < 4; ++u) { qc[u] = qn[u]; hb[u] = hn[u]; eb[u] = en[u]; }
+			for (int u = 0; u < 4; ++u) { qc[u] = qn[u]; hb[u] = hn[u]; eb[u] = en[u]; if (DUAL) e2b[DUAL ? u : 0] = e2n[DUAL ? u : 0]; }
 		}
 		L.gen_end();
 		if (SUB) L.sub_store(prof + (size_t)tk.pad * 128);
@@ -2303,6 +2316,25 @@ k2a_ll_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntas
                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	k2a_ll_task<PK, LDSP, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+/* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
+ * The packed register-profile form is not instantiated: with the second piece's state it does not fit 256 VGPRs (it spills), so
+ * k2a_shim_launch_lld / _rev send packed tasks to the LDS-profile form whatever `lds` says */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_lld_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+               uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false, false, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_lld_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true, false, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
 /* ---------------------------------------------------------------- suboptimal score (ksw2amd_ll_sub_batch)
@@ -2834,6 +2866,42 @@ int k2a_shim_launch_ll_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *t
 	else if (pk) hipLaunchKernelGGL((k2a_ll_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else hipLaunchKernelGGL((k2a_ll_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* two-piece gap cost: the same grids.  K2A_LLD_PK_REG (ksw2_types.h) says whether the packed register-profile form exists; without it
+ * packed tasks take the LDS profile whatever `lds` says */
+int k2a_shim_launch_lld(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && (lds || !K2A_LLD_PK_REG)) hipLaunchKernelGGL((k2a_lld_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+#if K2A_LLD_PK_REG
+	else if (pk) hipLaunchKernelGGL((k2a_lld_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+#endif
+	else if (lds) hipLaunchKernelGGL((k2a_lld_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_lld_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+int k2a_shim_launch_lld_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && (lds || !K2A_LLD_PK_REG)) hipLaunchKernelGGL((k2a_lld_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+#if K2A_LLD_PK_REG
+	else if (pk) hipLaunchKernelGGL((k2a_lld_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+#endif
+	else if (lds) hipLaunchKernelGGL((k2a_lld_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_lld_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	CHECK(hipGetLastError());
 	return 0;
 }

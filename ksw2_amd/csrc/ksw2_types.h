@@ -191,13 +191,17 @@ typedef struct K2aBook {
 #define K2A_LL_ROWS (64 * K2A_LL_C)    /* rows per generation: 64 strips */
 typedef struct K2aLL {
 	int32_t m, smax, oe, ge;         /* residue types, largest matrix entry, gap open + extend, gap extend */
+	int32_t oe2, ge2;                /* the second piece of ksw2amd_lld_batch (ksw2_lane_ll.h, DUAL); 0 and unread elsewhere */
 } K2aLL;
+/* two-piece kernels (DUAL): 1 when the packed register-profile form is built.  It is not: with f2[], the e2 chain and the 16-byte boundary
+ * prefetch it needs more than 256 VGPRs and spills, so packed two-piece tasks always take the LDS profile */
+#define K2A_LLD_PK_REG 0
 typedef struct K2aLLTask {
 	uint32_t roff[2], coff[2];       /* arena byte offsets of the row / column codes, per half (int32 tasks: [0]) */
 	uint32_t res[2];                 /* result slots of the halves; res[1] == res[0]: one alignment in both halves */
 	int32_t nrows, ncols, swapped;
 	int32_t pad;                     /* ksw2amd_ll_sub_batch: the task's row profile starts at byte 128 * pad of the profile (else 0) */
-	uint64_t boff;                   /* byte offset in the scratch of the generation boundary: 8 bytes per column (tasks over one generation) */
+	uint64_t boff;                   /* byte offset in the scratch of the generation boundary: 8 bytes per column (two-piece: 16; tasks over one generation) */
 } K2aLLTask;                         /* 48 bytes */
 typedef struct K2aLLRes {
 	int32_t score, qe, te;           /* ksw2amd_lres_t */

@@ -31,7 +31,16 @@ pointer entry (a profiled run then holds 1 + reps batches of one path); --kstats
 library call alone in the clock on both sides; pairs/s and GCUPS of both and their ratio, the forms both took, how many pairs change
 orientation (qlen > tlen: ll_batch runs them with rows = query), res equality and a parity sample against tests/lls_oracle.c.
 --ktrace: the kernel_trace.csv of a `rocprofv3 --kernel-trace` run of the same command -- per batch the time of k2a_ll_kernel, of
-k2a_ll_fsub_kernel and of k2a_ll_sub_kernel, their ratio, and the batch-to-batch spread of k2a_ll_kernel over its timed batches."""
+k2a_ll_fsub_kernel and of k2a_ll_sub_kernel, their ratio, and the batch-to-batch spread of k2a_ll_kernel over its timed batches.
+
+  python tools/scripts/ll_bench.py --workload A --dual [--align coords|cigar] [--ktrace kernel_trace.csv] [--out profiles/lld_bench_A.json]
+
+--dual: ksw2amd_lld_batch under the two-piece costs (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2) on the
+same prebuilt pair array -- with --align the two align entries (coords: KSW_EZ_SCORE_ONLY) -- the library call alone in the clock on
+both sides, a warm-up plus --reps batches of each in one process; pairs/s and GCUPS of both, their ratio, the spread of the single-piece
+batches, the forms both took, how many scores the second piece changes and a parity sample against tests/lld_oracle.c.  --ktrace: the
+kernel_trace.csv of a `rocprofv3 --kernel-trace` run of the same command -- per batch the time of k2a_ll_kernel (+ k2a_ll_rev_kernel)
+and of k2a_lld_kernel (+ k2a_lld_rev_kernel), their ratio and the batch-to-batch spread of the single-piece kernels."""
 import argparse
 import ctypes
 import csv
@@ -275,6 +284,87 @@ def main_sub(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["res_equal"] and rec["parity_ok"] else 1
 
 
+def main_dual(a, lib, q, t, mat, gapo, gape, cells, form):
+    from tests import lld_util as ld
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    gapo2, gape2 = 24, 1
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res, res2 = (np.zeros((n, 3), dtype=np.int32) for _ in range(2))
+    aln, aln2 = ((ksw2_amd.LocalAln * n)() for _ in range(2))   # CIGAR buffers are reused from batch to batch
+    flag = SCORE_ONLY if a.align == "coords" else 0
+    rp = lambda x: x.ctypes.data_as(ctypes.POINTER(ksw2_amd.LocalResult))
+
+    def single():
+        if a.align:
+            return L.ksw2amd_ll_align_batch(None, 5, mp.ctypes.data_as(i8p), gapo, gape, flag, n, pairs, aln)
+        return L.ksw2amd_ll_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(res))
+
+    def dual():
+        if a.align:
+            return L.ksw2amd_lld_align_batch(None, 5, mp.ctypes.data_as(i8p), gapo, gape, gapo2, gape2, flag, n, pairs, aln2)
+        return L.ksw2amd_lld_batch(5, mp.ctypes.data_as(i8p), gapo, gape, gapo2, gape2, n, pairs, rp(res2))
+
+    def timed(fn, tag):
+        os.environ["KSW2AMD_TRACE"] = "1"                      # the warm-up's form lines
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            lines = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tag in l]
+        os.environ.pop("KSW2AMD_TRACE")
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            times.append(time.perf_counter() - t0)
+        return dict(e2e_s=min(times), e2e_all_s=times, e2e_spread=(max(times) - min(times)) / min(times), pairs_per_s=n / min(times),
+                    e2e_gcups=cells / min(times) / 1e9, forms=lines)
+
+    rec = dict(workload=a.workload, mode="dual" + ("-align-" + a.align if a.align else ""), pairs=n, cells=cells, costs=[gapo, gape, gapo2, gape2],
+               ll_form=form, clock="library call only: the pair array is built before it")
+    one, two = ("ll_align_batch", "lld_align_batch") if a.align else ("ll_batch", "lld_batch")
+    rec[one] = timed(single, "ll: pairs")
+    rec[two] = timed(dual, "lld: pairs")
+    rec["dual_over_single_e2e"] = rec[two]["e2e_s"] / rec[one]["e2e_s"]
+    if a.align:
+        res = np.array([(x.score, x.qe, x.te) for x in aln], dtype=np.int32)
+        res2 = np.array([(x.score, x.qe, x.te) for x in aln2], dtype=np.int32)
+    rec["scores_changed_by_second_piece"] = int((res[:, 0] != res2[:, 0]).sum())
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = ld.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, (gapo, gape, gapo2, gape2))
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool((res2[idx] == exp).all())
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        k1 = trace_batches(a.ktrace, "k2a_ll_kernel", nl(rec[one]["forms"][0]))[1:]            # [0]: the warm-up
+        k2 = trace_batches(a.ktrace, "k2a_lld_kernel", nl(rec[two]["forms"][0]))[1:]
+        kern = dict(ll_kernel_ms=k1, lld_kernel_ms=k2)
+        if a.align:
+            r1 = trace_batches(a.ktrace, "k2a_ll_rev_kernel", nl(rec[one]["forms"][0]))[1:]
+            r2 = trace_batches(a.ktrace, "k2a_lld_rev_kernel", nl(rec[two]["forms"][0]))[1:]
+            kern.update(ll_rev_kernel_ms=r1, lld_rev_kernel_ms=r2, rev_dual_over_single=(sum(r2) / len(r2)) / (sum(r1) / len(r1)) if r1 and r2 else None)
+        kern.update(ll_kernel_spread=(max(k1) - min(k1)) / min(k1) if k1 else None,
+                    dual_over_single=(sum(k2) / len(k2)) / (sum(k1) / len(k1)) if k1 and k2 else None,
+                    note="k2a_ll_kernel of this build, same session (its code and register counts are the parent commit's)")
+        rec["kernel"] = kern
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True)
@@ -289,6 +379,7 @@ def main():
     ap.add_argument("--flat", choices=("host", "host-pinned", "device", "all"), default=None,
                     help="ksw2amd_ll_batch_flat / _align_batch_flat from one arena against the pointer entry, library calls only in the clock")
     ap.add_argument("--sub", action="store_true", help="ksw2amd_ll_sub_batch beside ksw2amd_ll_batch on the same pair array, library calls only in the clock")
+    ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -305,6 +396,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.dual:
+        return main_dual(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sub:
         return main_sub(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.flat:
