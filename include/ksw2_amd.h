@@ -383,11 +383,38 @@ int ksw2amd_ll_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape,
  * the on-device code check, the reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat /
  * ksw2amd_ll_align_batch_flat unchanged.  Device failures: a negative code, no CPU fallback.  KSW2AMD_LL_FORM / KSW2AMD_LL_CHUNK_BYTES
  * govern these entries too; KSW2AMD_LL_LDS only their int32 tasks (packed two-piece tasks always read scores from LDS).
- * Not offered: a two-piece suboptimal score, single-pair entries on a ksw_ll_qinit profile. */
+ * The two-piece suboptimal score and the single-pair entries on a ksw_ll_qinit profile follow the four batch entries. */
 int ksw2amd_lld_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 int ksw2amd_lld_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
 int ksw2amd_lld_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
 int ksw2amd_lld_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
+
+/* Suboptimal local score under the two-piece gap cost, and the two-piece single-pair entries (new).
+ * With H the matrix of ksw2amd_lld_batch -- max(0, diag + s, E, F, E2, F2), exact int32 -- res[i] is bit for bit what ksw2amd_lld_batch
+ * returns, and R(t), d, score2, te2, qe2 and the (0, -1, -1) cases are those of ksw2amd_ll_sub_batch read on this H: d = excl when
+ * excl >= 0, else ceil(score / smax) with the two-piece score.  With (gapo2, gape2) = (gapo, gape), or gapo2 >= gapo and gape2 >= gape,
+ * every result equals ksw2amd_ll_sub_batch's.  Arguments: m 1..127 (m = 1 is accepted), all four gap costs 0..127, excl <= 0x3fffffff,
+ * every residue code < m, all checked before anything is launched (KSW2AMD_E_PARAM); the flat entry checks the codes on the device, chunk
+ * by chunk, and has the chunking, reset and error semantics of ksw2amd_ll_sub_batch_flat.
+ * The shoulder of the best hit.  Below the best cell the best column carries H(te + k, qe) = score - gapcost(k), and R(te + k) is at least
+ * that.  Under a second piece with a small gape2 this decays by gape2 per row, so whenever gape2 < smax the default window
+ * ceil(score / smax) ends before the shoulder does and score2 is then the shoulder's first row outside the window, not a second hit.
+ * Example: +100 / -100 matrix, costs (4, 2, 24, 1), a 200-residue query matched with one 60-residue gap (score 19916, te 559) gives
+ * d = 200 and score2 = 19916 - (24 + 201) = 19691 at te2 = 760, the first row behind the window and a row of unrelated residues.  A
+ * caller who wants independent hits only passes an excl sized to (score - gapo2) / gape2.  The default is kept as it is: it is what
+ * makes these entries equal the single-piece ones under equal pieces. */
+int ksw2amd_lld_sub_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int excl, int n,
+                          const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ksw2amd_lsub_t *sub);
+int ksw2amd_lld_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int excl, int n,
+                               const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ksw2amd_lsub_t *sub);
+/* one pair on a ksw_ll_qinit profile; each returns the score.  They are ksw_ll_i16, ksw2amd_ll_align and ksw2amd_ll_sub under the two-piece
+ * cost, results equal to row 0 of the batch entries on that pair.  On a device failure or a bad argument they return 0 with the
+ * coordinates at -1, n_cigar = 0 and *sub = (0, -1, -1), and report like ksw_ll_i16 (ksw2amd_error_count, ksw2amd_last_error, the
+ * handler, KSW2AMD_ABORT_ON_ERROR).  ksw2amd_lld_align on a profile with m = 1 fails that way, as ksw2amd_lld_align_batch rejects m = 1 */
+int ksw2amd_lld(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int *qe, int *te);
+int ksw2amd_lld_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int flag, ksw2amd_laln_t *aln);
+int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int excl,
+                    int *qe, int *te, ksw2amd_lsub_t *sub);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

@@ -112,7 +112,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw_ll_qinit", "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align",
            "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
            "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
-           "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat"]
+           "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
+           "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -122,7 +123,8 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_plan_describe", "ksw2amd_extz_batch_flat", "ksw2amd_extd_batch_flat", "ksw2amd_plan_create_flat",
                 "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
                 "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
-                "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat"]
+                "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
+                "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -267,6 +269,16 @@ class Library:
             L.ksw2amd_lld_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
             L.ksw2amd_lld_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
             L.ksw2amd_lld_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_lld"):               # (the two-piece single-pair entries live in ksw2_host_lld.c: every build with it has them)
+            L.ksw2amd_lld.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+            L.ksw2amd_lld_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_lld_sub_batch"):     # (nor the two-piece suboptimal score and its launch's twin: tests/llds_util.py adds them)
+            L.ksw2amd_lld_sub_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult),
+                                                ctypes.POINTER(LocalSub)]
+            L.ksw2amd_lld_sub_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult),
+                                                     ctypes.POINTER(LocalSub)]
+            L.ksw2amd_lld_sub.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                          ctypes.POINTER(LocalSub)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -627,6 +639,79 @@ class Library:
         out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
         self._check(rc)
         return out
+
+    def lld_sub_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, excl=-1, m=None, pairs=None, n=None):
+        """ksw2amd_lld_sub_batch: ll_sub_batch under the two-piece gap cost -- lld_batch's result plus the largest row maximum of ITS
+        matrix outside |t - te| <= d -> two (n, 3) int32 arrays: score, qe, te and score2, qe2, te2."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        sub = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_lld_sub_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, excl, n, pairs,
+                                            out.ctypes.data_as(ctypes.POINTER(LocalResult)), sub.ctypes.data_as(ctypes.POINTER(LocalSub)))
+        self._check(rc)
+        return out[:n], sub[:n]
+
+    def lld_sub_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, excl=-1, m=None, device_base=None, out=None, sub=None):
+        """ksw2amd_lld_sub_batch_flat: lld_sub_batch on an arena (see ll_sub_batch_flat) -> two (n, 3) int32 arrays."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        sub = np.zeros((max(n, 1), 3), dtype=np.int32) if sub is None else sub
+        for a in (out, sub):
+            assert a.dtype == np.int32 and a.flags.c_contiguous and a.shape[0] >= n and a.shape[1] == 3
+        rc = self.lib.ksw2amd_lld_sub_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, excl, n, ctypes.byref(f),
+                                                 out.ctypes.data_as(ctypes.POINTER(LocalResult)), sub.ctypes.data_as(ctypes.POINTER(LocalSub)))
+        self._check(rc)
+        return out[:n], sub[:n]
+
+    def _lld_profile(self, query, target, mat, m, size):
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        qa, qp = self._seq(query)
+        ta, tp = self._seq(target)
+        prof = self.lib.ksw_ll_qinit(None, size, len(qa), qp, m, mat.ctypes.data_as(_i8p))
+        if not prof:
+            raise Ksw2Error("ksw_ll_qinit: " + self.last_error())
+        return prof, ta, tp, (qa, mat)
+
+    def lld(self, query, target, mat, gapo, gape, gapo2, gape2, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_lld: ll_i16 under the two-piece gap cost -> (score, qe, te)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw2amd_lld(prof, len(ta), tp, gapo, gape, gapo2, gape2, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
+
+    def lld_align(self, query, target, mat, gapo, gape, gapo2, gape2, flag=0, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_lld_align(km=NULL, ...) -> dict like lld_align_batch's."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            a = LocalAln()
+            score = self.lib.ksw2amd_lld_align(None, prof, len(ta), tp, gapo, gape, gapo2, gape2, flag, ctypes.byref(a))
+        finally:
+            _libc.free(prof)
+        d = self._aln_to_dict(a)
+        assert d["score"] == int(score)
+        return d
+
+    def lld_sub(self, query, target, mat, gapo, gape, gapo2, gape2, excl=-1, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_lld_sub -> (score, qe, te), (score2, qe2, te2)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te, s = _int(0), _int(0), LocalSub()
+            score = self.lib.ksw2amd_lld_sub(prof, len(ta), tp, gapo, gape, gapo2, gape2, excl, ctypes.byref(qe), ctypes.byref(te), ctypes.byref(s))
+        finally:
+            _libc.free(prof)
+        return (int(score), qe.value, te.value), (int(s.score2), int(s.qe2), int(s.te2))
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

@@ -315,7 +315,8 @@ typedef struct {
 /* two-piece gap cost (ksw2_host_lld.c).  fwd = k2a_shim_launch_lld, passed in the same way (the start-cell
  * launch k2a_shim_launch_lld_rev travels as the ll_rev_fn): only ksw2_host_lld.o names the two.  With it a chunk scores gaps with
  * min(gapo + l * gape, gapo2 + l * gape2), launches fwd for the forward pass and keeps 16 bytes per column of generation boundary.
- * Never together with an ll_sub_t */
+ * Together with an ll_sub_t (ksw2_host_llds.c) the forward launch is the ll_sub_t's -- k2a_shim_launch_lld_sub, which
+ * only ksw2_host_llds.o names -- and fwd may be NULL */
 typedef int (*ll_fwd_fn)(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                          uint8_t *scratch, K2aLLRes *res, void *stream);
 typedef struct {

@@ -9,7 +9,8 @@
  * This is the only host object that calls k2a_shim_launch_ll (tests/sim links the other four against a simulator without it).
  * ksw2amd_ll_align_batch (ksw2_host_lla.c) runs its start-cell pass from what a chunk staged here: it hands ll_batch_ex the launch as a
  * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
- * The two-piece entries (ksw2_host_lld.c) hand in their forward and start-cell launches and the second gap pair the same way (ll_dual_t).
+ * The two-piece entries (ksw2_host_lld.c, ksw2_host_llds.c) hand in their forward, start-cell and profile-writing launches and the second
+ * gap pair the same way (ll_dual_t).
  */
 #include "ksw2_host_int.h"
 
@@ -101,8 +102,10 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
  * and results in device memory; one download brings back both arrays.
  * sb (never with rev): ksw2amd_ll_sub_batch -- rows = target for every pair, the forward launch is sb->launch, which also fills a row
  * profile per task (behind the boundaries in the scratch, at 128 * K2aLLTask.pad) and reduces it into K2aLLSub[n] behind K2aLLRes[n]
- * du (never with sb): the two-piece gap cost of ksw2amd_lld_batch -- the forward launch is du->fwd (rev: the caller's two-piece start-cell
- * launch), the boundary holds 16 bytes per column */
+ * du: the two-piece gap cost of ksw2amd_lld_batch -- the forward launch is du->fwd (rev: the caller's two-piece start-cell launch), the
+ * boundary holds 16 bytes per column
+ * sb and du together: ksw2amd_lld_sub_batch -- par.oe2 / ge2 and the 16-byte boundary come from du, the forward
+ * launch is sb->launch (the caller's two-piece one; du->fwd is not called), rows are the target, and ll_pair_bytes sizes both */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du)
 {
@@ -157,7 +160,8 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host", du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] %s-rev: pk_tasks=%d int32_tasks=%d profile=%s%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers",
 	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
-	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] ll-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d\n", ntk_pk, ni32, lds ? "lds" : "registers", sb->excl);
+	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] %s-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers", sb->excl,
+	                              du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (ntk == 0 && !flat) { free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
@@ -282,7 +286,8 @@ out:
 	return rc;
 }
 
-/* ksw2amd_ll_batch (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c), and ksw2amd_ll_sub_batch (ksw2_host_lls.c) */
+/* ksw2amd_ll_batch (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c), and ksw2amd_ll_sub_batch (ksw2_host_lls.c);
+ * du: their two-piece forms, sb with du included (ksw2_host_lld.c, ksw2_host_llds.c) */
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
 {

@@ -29,7 +29,8 @@ static int llf_pair_span(const ksw2amd_lflat_t *in, int i, uint64_t *lo, uint64_
 	return 1;
 }
 
-/* ksw2amd_ll_batch_flat (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch_flat, and ksw2amd_ll_sub_batch_flat (sb) */
+/* ksw2amd_ll_batch_flat (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch_flat, and ksw2amd_ll_sub_batch_flat (sb); du: their
+ * two-piece forms, sb with du included */
 int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
                  const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
 {

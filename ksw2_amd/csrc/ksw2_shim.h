@@ -200,6 +200,11 @@ int k2a_shim_launch_ll_check(const K2aLLChk *ent, int nent, uint32_t nblocks, co
  * the smallest such row, that row's first column.  Only ksw2_host_lls.c calls it (the other simulator builds have no such symbol). */
 int k2a_shim_launch_ll_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                            uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream);
+/* ksw2amd_lld_sub_batch: the same under the two-piece gap cost -- the forward launch of k2a_shim_launch_lld (16
+ * bytes of boundary per column, packed tasks on the LDS profile unless K2A_LLD_PK_REG) that also writes the row profiles, and behind it
+ * the reduction of k2a_shim_launch_ll_sub as it is.  Only ksw2_host_llds.c calls it (the other simulator builds have no such symbol). */
+int k2a_shim_launch_lld_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2190,7 +2190,8 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * runs over the bounding rectangle of its halves, never more generations or steps than the forward launch, and a task whose halves
  * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb.
  * DUAL (k2a_lld_kernel / k2a_lld_rev_kernel): the two-piece gap cost.  E2 travels with H and E: one more rotate
- * per step, and a boundary entry of 16 bytes per column (H, E, E2, pad) stored and prefetched as one access. */
+ * per step, and a boundary entry of 16 bytes per column (H, E, E2, pad) stored and prefetched as one access.
+ * SUB (k2a_ll_fsub_kernel; with DUAL: k2a_lld_fsub_kernel): the forward pass that also streams every generation's row maxima to `prof`. */
 template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
@@ -2346,6 +2347,16 @@ k2a_ll_fsub_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int nta
                    uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, uint8_t *__restrict__ prof)
 {
 	k2a_ll_task<PK, LDSP, false, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr, prof);
+}
+
+/* The same under the two-piece gap cost (ksw2amd_lld_sub_batch): SUB and DUAL together -- the e2 chain, the
+ * 16-byte boundary and sub_store().  The packed register-profile form is not instantiated (K2A_LLD_PK_REG) */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_lld_fsub_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                    uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, uint8_t *__restrict__ prof)
+{
+	k2a_ll_task<PK, LDSP, false, true, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr, prof);
 }
 
 /* The reduction, launched behind the forward launch (the kernel boundary makes the profile and res[] visible): one wavefront per
@@ -2918,6 +2929,30 @@ int k2a_shim_launch_ll_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *t
 	else if (pk) hipLaunchKernelGGL((k2a_ll_fsub_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_fsub_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
 	else hipLaunchKernelGGL((k2a_ll_fsub_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	CHECK(hipGetLastError());
+	const int64_t waves = (int64_t)ntasks * (pk ? 2 : 1);
+	hipLaunchKernelGGL(k2a_ll_sub_kernel, dim3((unsigned)((waves + K2A_WPB - 1) / K2A_WPB)), block, 0, (hipStream_t)stream, par->smax, tasks, ntasks, pk, res,
+	                   (const uint8_t*)prof, excl, sub);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* ksw2amd_lld_sub_batch: the two-piece forward pass that also writes the row profiles (packed tasks on the LDS profile unless
+ * K2A_LLD_PK_REG, as in k2a_shim_launch_lld), then the reduction of k2a_shim_launch_ll_sub unchanged: it reads res[], the task fields
+ * and the profile, none of which knows the gap cost */
+int k2a_shim_launch_lld_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "local alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && (lds || !K2A_LLD_PK_REG)) hipLaunchKernelGGL((k2a_lld_fsub_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+#if K2A_LLD_PK_REG
+	else if (pk) hipLaunchKernelGGL((k2a_lld_fsub_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+#endif
+	else if (lds) hipLaunchKernelGGL((k2a_lld_fsub_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
+	else hipLaunchKernelGGL((k2a_lld_fsub_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, prof);
 	CHECK(hipGetLastError());
 	const int64_t waves = (int64_t)ntasks * (pk ? 2 : 1);
 	hipLaunchKernelGGL(k2a_ll_sub_kernel, dim3((unsigned)((waves + K2A_WPB - 1) / K2A_WPB)), block, 0, (hipStream_t)stream, par->smax, tasks, ntasks, pk, res,

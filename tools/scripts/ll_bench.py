@@ -40,7 +40,14 @@ same prebuilt pair array -- with --align the two align entries (coords: KSW_EZ_S
 both sides, a warm-up plus --reps batches of each in one process; pairs/s and GCUPS of both, their ratio, the spread of the single-piece
 batches, the forms both took, how many scores the second piece changes and a parity sample against tests/lld_oracle.c.  --ktrace: the
 kernel_trace.csv of a `rocprofv3 --kernel-trace` run of the same command -- per batch the time of k2a_ll_kernel (+ k2a_ll_rev_kernel)
-and of k2a_lld_kernel (+ k2a_lld_rev_kernel), their ratio and the batch-to-batch spread of the single-piece kernels."""
+and of k2a_lld_kernel (+ k2a_lld_rev_kernel), their ratio and the batch-to-batch spread of the single-piece kernels.
+
+  python tools/scripts/ll_bench.py --workload A --dual --sub [--excl -1] [--ktrace kernel_trace.csv] [--out profiles/llds_bench_A.json]
+
+--dual --sub: ksw2amd_lld_sub_batch beside ksw2amd_lld_batch, both under (4, 2, 24, 1), on the same prebuilt pair
+array, the library call alone in the clock on both sides; pairs/s and GCUPS of both and their ratio, the forms both took, res equality and
+a parity sample against tests/llds_oracle.c.  --ktrace: per batch the time of k2a_lld_kernel, of k2a_lld_fsub_kernel and of
+k2a_ll_sub_kernel, the ratio (k2a_lld_fsub_kernel + k2a_ll_sub_kernel) / k2a_lld_kernel and the batch-to-batch spread of k2a_lld_kernel."""
 import argparse
 import ctypes
 import csv
@@ -365,6 +372,79 @@ def main_dual(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["parity_ok"] else 1
 
 
+def main_dual_sub(a, lib, q, t, mat, gapo, gape, cells, form):
+    from tests import llds_util as lx
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    gapo2, gape2 = 24, 1
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res, res2, sub = (np.zeros((n, 3), dtype=np.int32) for _ in range(3))
+    rp = lambda x, ty: x.ctypes.data_as(ctypes.POINTER(ty))
+
+    def plain():
+        return L.ksw2amd_lld_batch(5, mp.ctypes.data_as(i8p), gapo, gape, gapo2, gape2, n, pairs, rp(res, ksw2_amd.LocalResult))
+
+    def withsub():
+        return L.ksw2amd_lld_sub_batch(5, mp.ctypes.data_as(i8p), gapo, gape, gapo2, gape2, a.excl, n, pairs, rp(res2, ksw2_amd.LocalResult),
+                                       rp(sub, ksw2_amd.LocalSub))
+
+    def timed(fn, tag):
+        os.environ["KSW2AMD_TRACE"] = "1"                      # the warm-up's form lines
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            lines = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tag in l]
+        os.environ.pop("KSW2AMD_TRACE")                        # (the binding re-reads the environment in front of every call)
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            times.append(time.perf_counter() - t0)
+        return dict(e2e_s=min(times), e2e_all_s=times, e2e_spread=(max(times) - min(times)) / min(times), pairs_per_s=n / min(times),
+                    e2e_gcups=cells / min(times) / 1e9, forms=lines)
+
+    rec = dict(workload=a.workload, mode="dual-sub", pairs=n, cells=cells, costs=[gapo, gape, gapo2, gape2], excl=a.excl, ll_form=form,
+               pairs_changing_orientation=int(sum(len(x) > len(y) for x, y in zip(q, t))),
+               clock="library call only: the pair array is built before it")
+    rec["lld_batch"] = timed(plain, "lld: pairs")
+    rec["lld_sub_batch"] = timed(withsub, "lld-sub:")
+    rec["sub_over_plain_e2e"] = rec["lld_sub_batch"]["e2e_s"] / rec["lld_batch"]["e2e_s"]
+    rec["res_equal"] = bool((res == res2).all())
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = lx.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, (gapo, gape, gapo2, gape2), a.excl)
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool((np.hstack([res2, sub])[idx] == exp).all())
+    rec["score2_positive"] = int((sub[:, 0] > 0).sum())
+    if a.ktrace:
+        # launches per batch: one per kernel form that had tasks (packed, int32), as the form lines say
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        kp = trace_batches(a.ktrace, "k2a_lld_kernel", nl(rec["lld_batch"]["forms"][0]))[1:]          # [0]: the warm-up
+        kf = trace_batches(a.ktrace, "k2a_lld_fsub_kernel", nl(rec["lld_sub_batch"]["forms"][0]))[1:]
+        kr = trace_batches(a.ktrace, "k2a_ll_sub_kernel", nl(rec["lld_sub_batch"]["forms"][0]))[1:]
+        ks = [x + y for x, y in zip(kf, kr)]
+        rec["kernel"] = dict(lld_kernel_ms=kp, lld_fsub_kernel_ms=kf, sub_kernel_ms=kr,
+                             lld_kernel_spread=(max(kp) - min(kp)) / min(kp) if kp else None,
+                             sub_over_plain=(sum(ks) / len(ks)) / (sum(kp) / len(kp)) if kp and ks else None,
+                             fsub_over_plain=(sum(kf) / len(kf)) / (sum(kp) / len(kp)) if kp and kf else None,
+                             note="k2a_lld_kernel of this build, same session (its code and register counts are the parent commit's)")
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["res_equal"] and rec["parity_ok"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True)
@@ -379,7 +459,7 @@ def main():
     ap.add_argument("--flat", choices=("host", "host-pinned", "device", "all"), default=None,
                     help="ksw2amd_ll_batch_flat / _align_batch_flat from one arena against the pointer entry, library calls only in the clock")
     ap.add_argument("--sub", action="store_true", help="ksw2amd_ll_sub_batch beside ksw2amd_ll_batch on the same pair array, library calls only in the clock")
-    ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries")
+    ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries; with --sub ksw2amd_lld_sub_batch beside ksw2amd_lld_batch")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -396,6 +476,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.dual and a.sub:
+        return main_dual_sub(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.dual:
         return main_dual(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sub:
