@@ -416,6 +416,28 @@ int ksw2amd_lld_align(void *km, void *q, int tlen, const uint8_t *target, int ga
 int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int excl,
                     int *qe, int *te, ksw2amd_lsub_t *sub);
 
+/* Semi-global alignment (new): the whole query, end to end, against the best-scoring interval of
+ * the target -- what other libraries call fit, glocal or infix alignment.  Scoring arguments as for ksw2amd_ll_batch: s(t, q) =
+ * mat[t * m + q], a gap of length l costs gapo + l * gape, m 1..127, gapo / gape 0..127, every residue code < m.  With t the target index
+ * and j the query index, both 0-based, and -1 the boundary:
+ *   H(t, -1) = 0 for every t >= -1 (the start in the target is free),   H(-1, j) = -(gapo + (j + 1) * gape),
+ *   H(t, j)  = max(H(t - 1, j - 1) + s(t, j), E(t, j), F(t, j)), Gotoh E / F as in ksw_extz (a gap may follow a gap of the other kind at
+ *              the cost of another open; E and F are -infinity on the boundary); there is NO clamp at 0;
+ *   score = max over 0 <= t < tlen of H(t, qlen - 1),   te = the smallest such t,   qe = qlen - 1.
+ * Scores may be negative, and the interval may be empty: when inserting the whole query is best, score = -(gapo + qlen * gape), te = 0.
+ * Nothing is launched for qlen <= 0 -> (0, -1, -1), nor for tlen <= 0 with qlen > 0 -> (-(gapo + qlen * gape), qlen - 1, -1).
+ * Exact int32; a pair with gapo + qlen * (gape + smax) + smax > 0x3fffffff, smax = max(0, largest matrix entry), is rejected.  A matrix
+ * without a positive entry is legal here (the local entries skip such pairs; these do not).  Every argument and every code is checked
+ * before anything is staged or launched (KSW2AMD_E_PARAM); the flat entry checks the codes on the device, chunk by chunk, and has the
+ * chunking, reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat.
+ * Not computed: the start tb of the interval and a CIGAR, the two-piece gap cost, free query ends.
+ * ksw2amd_sg: one pair on a ksw_ll_qinit profile; returns the score, equal to row 0 of ksw2amd_sg_batch on that pair.  On a device
+ * failure or a bad argument it returns 0 with *qe = *te = -1 and reports like ksw_ll_i16 (ksw2amd_error_count, ksw2amd_last_error, the
+ * handler, KSW2AMD_ABORT_ON_ERROR). */
+int ksw2amd_sg_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
+int ksw2amd_sg_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
+int ksw2amd_sg(void *q, int tlen, const uint8_t *target, int gapo, int gape, int *qe, int *te);
+
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t
  * or NULL), fetch = wait + download + fill ez[]. */

@@ -113,7 +113,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
            "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
            "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
-           "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub"]
+           "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
+           "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -124,7 +125,8 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw_ll_i16", "ksw2amd_ll_batch", "ksw2amd_ll_align_batch", "ksw2amd_ll_align", "ksw2amd_ll_batch_flat", "ksw2amd_ll_align_batch_flat",
                 "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
                 "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
-                "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub"]
+                "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
+                "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -279,6 +281,10 @@ class Library:
                                                      ctypes.POINTER(LocalSub)]
             L.ksw2amd_lld_sub.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int),
                                           ctypes.POINTER(LocalSub)]
+        if hasattr(L, "ksw2amd_sg_batch"):          # (nor the semi-global entries and their launch's twin: tests/sg_util.py adds them)
+            L.ksw2amd_sg_batch.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_sg_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_sg.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -712,6 +718,45 @@ class Library:
         finally:
             _libc.free(prof)
         return (int(score), qe.value, te.value), (int(s.score2), int(s.qe2), int(s.te2))
+
+    # ---- semi-global alignment: the whole query against the best interval of the target (no clamp at 0, scores may be negative)
+    def sg_batch(self, queries, targets, mat, gapo, gape, m=None, pairs=None, n=None):
+        """ksw2amd_sg_batch: the best score of the whole query, end to end, in the target, and the target index it ends at
+        -> (n, 3) int32 array of score, qe (= qlen - 1), te (the smallest on a tie).  pairs / n as for ll_batch."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_sg_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, n, pairs,
+                                       out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def sg_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, m=None, device_base=None, out=None):
+        """ksw2amd_sg_batch_flat: sg_batch on an arena (see ll_batch_flat) -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1] == 3
+        rc = self.lib.ksw2amd_sg_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, n, ctypes.byref(f),
+                                            out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def sg(self, query, target, mat, gapo, gape, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_sg -> (score, qe, te)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw2amd_sg(prof, len(ta), tp, gapo, gape, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

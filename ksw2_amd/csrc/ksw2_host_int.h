@@ -324,15 +324,24 @@ typedef struct {
 	ll_fwd_fn fwd;
 	int pk_reg;                        /* 1: the packed kernels have a register-profile form (0: packed tasks take the LDS profile; trace line only) */
 } ll_dual_t;
+/* semi-global mode (ksw2_host_sg.c).  launch = k2a_shim_launch_sg, passed in the same way: only ksw2_host_sg.o names
+ * it.  With it (never with rev, sb or du) a chunk runs every pair with rows = target on biased values: smax is max(0, largest entry), the
+ * packed form is admitted by ll_sg_pk_admit, a pair without a query or without a target gets its corner result instead of being skipped,
+ * and a matrix without a positive entry still launches */
+typedef struct {
+	ll_fwd_fn launch;
+} ll_fit_t;
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
-             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du);
-size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual);
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft);
+size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit);
+int ll_sg_pk_admit(int qlen, int gapo, int gape, int smax);
+int ll_sg_check_range(int i, int qlen, int gapo, int gape, int smax);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du);
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du, const ll_fit_t *ft);
 int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du);      /* ksw2_host_llf.c */
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du, const ll_fit_t *ft);      /* ksw2_host_llf.c */
 /* the stages of ksw2amd_ll_align_batch behind the two kernel passes (ksw2_host_lla.c), shared with ksw2amd_ll_align_batch_flat */
 #define LLA_FLAGS (KSW_EZ_SCORE_ONLY | KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)
 int lla_cells(int n, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);

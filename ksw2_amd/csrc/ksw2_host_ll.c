@@ -10,7 +10,7 @@
  * ksw2amd_ll_align_batch (ksw2_host_lla.c) runs its start-cell pass from what a chunk staged here: it hands ll_batch_ex the launch as a
  * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
  * The two-piece entries (ksw2_host_lld.c, ksw2_host_llds.c) hand in their forward, start-cell and profile-writing launches and the second
- * gap pair the same way (ll_dual_t).
+ * gap pair the same way (ll_dual_t), and the semi-global entries (ksw2_host_sg.c) their launch and mode (ll_fit_t).
  */
 #include "ksw2_host_int.h"
 
@@ -23,12 +23,31 @@ static int ll_pk_admit(int qlen, int tlen, int smax)
 	return (mn + 1) * (int64_t)smax <= 65535 && mn <= 65535;
 }
 
+/* the semi-global mode runs on H' = H + B, B = gapo + qlen * gape.  A path that ends in column j has at most
+ * j + 1 aligned pairs of residues and starts at H(t, -1) = 0, so H(t, j) <= (j + 1) * smax with smax = max(0, largest entry), and the
+ * largest value the packed step forms, H'(t - 1, j - 1) + smax, stays within B + qlen * smax + smax.  The packed form is exact while that
+ * fits 16 bits: B + (qlen + 1) * smax <= 65535.  (No column index is kept in 16 bits: the maximum is over the last column only.)
+ * With smax = 127 and costs (5, 1): 128 * qlen + 132 <= 65535, a query of 510 is packed and one of 511 is not. */
+int ll_sg_pk_admit(int qlen, int gapo, int gape, int smax)
+{
+	return (int64_t)gapo + (int64_t)qlen * gape + ((int64_t)qlen + 1) * smax <= 65535;
+}
+
+/* ... and in int32 while gapo + qlen * (gape + smax) + smax <= 0x3fffffff (pair i of the call, for the message) */
+int ll_sg_check_range(int i, int qlen, int gapo, int gape, int smax)
+{
+	char msg[32];
+	if (qlen <= 0 || (int64_t)gapo + (int64_t)qlen * ((int64_t)gape + smax) + smax <= 0x3fffffff) return KSW2AMD_OK;
+	snprintf(msg, sizeof(msg), "%d", i);
+	return fail(KSW2AMD_E_PARAM, "semi-global alignment: pair %s: gapo + qlen * (gape + smax) + smax exceeds 0x3fffffff", msg);
+}
+
 /* a pair's share of a chunk's byte budget: sequences, table entries, results, the generation boundary (8 bytes per column of a task
- * over one generation; dual: 16) and -- sub: rows = target whatever the lengths -- the row profile */
-size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual)
+ * over one generation; dual: 16) and -- sub: rows = target whatever the lengths -- the row profile; fit: rows = target, no profile */
+size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit)
 {
 	const size_t ql = (size_t)imax(qlen, 0), tl = (size_t)imax(tlen, 0);
-	const size_t rows = sub || tl >= ql ? tl : ql, cols = sub || tl >= ql ? ql : tl;
+	const size_t rows = sub || fit || tl >= ql ? tl : ql, cols = sub || fit || tl >= ql ? ql : tl;
 	return rows + cols + 8 + sizeof(K2aLLTask) + sizeof(K2aLLRes) + sizeof(K2aLLBeg) + (rows > K2A_LL_ROWS ? align_up(cols * (dual ? 16 : 8), 256) : 0)
 	       + (sub ? align_up(K2A_LLSUB_BYTES(rows), 256) : 0);
 }
@@ -92,6 +111,16 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
 	return nent;
 }
 
+/* semi-global mode: the pairs of a chunk that launch nothing and still have a result -- a query without a target */
+static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2amd_lres_t *res)
+{
+	int i;
+	for (i = 0; i < n; ++i) {
+		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
+		if (ql > 0 && tl <= 0) { res[i].score = -(gapo + ql * gape); res[i].qe = ql - 1; res[i].te = -1; }      /* the whole query inserted before the target */
+	}
+}
+
 /* one chunk: pairs [0, n) of the caller's.  Where the sequences live is all that differs between the two kinds of source:
  *   gathered (src->pairs): validated by the caller, copied once each into the staging arena behind the task table and the pen tables;
  *   borrowed (src->flat):  the chunk's span [lo, hi) of the caller's arena is the kernels' `seq` as it is -- uploaded in one copy
@@ -105,15 +134,18 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
  * du: the two-piece gap cost of ksw2amd_lld_batch -- the forward launch is du->fwd (rev: the caller's two-piece start-cell launch), the
  * boundary holds 16 bytes per column
  * sb and du together: ksw2amd_lld_sub_batch -- par.oe2 / ge2 and the 16-byte boundary come from du, the forward
- * launch is sb->launch (the caller's two-piece one; du->fwd is not called), rows are the target, and ll_pair_bytes sizes both */
+ * launch is sb->launch (the caller's two-piece one; du->fwd is not called), rows are the target, and ll_pair_bytes sizes both
+ * ft (never with rev, sb or du): ksw2amd_sg_batch -- rows = target for every pair, the forward launch is
+ * ft->launch, smax is max(0, largest entry) and may be 0, the packed form is admitted by ll_sg_pk_admit, and a pair without a query or
+ * without a target gets its corner result (ll_fit_corners) once the chunk has passed its checks, instead of being skipped */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
-             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du)
+             const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft)
 {
 	const char *fv = ENV(LL_FORM), *lv = ENV(LL_LDS);
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
-	const ll_fwd_fn fwd = du ? du->fwd : k2a_shim_launch_ll;
-	const char *tn = du ? "lld" : "ll";                  /* the trace lines' prefix */
+	const ll_fwd_fn fwd = ft ? ft->launch : du ? du->fwd : k2a_shim_launch_ll;
+	const char *tn = ft ? "sg" : du ? "lld" : "ll";      /* the trace lines' prefix */
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
@@ -132,11 +164,11 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		res[i].score = 0; res[i].qe = res[i].te = -1;
 		if (rev) { beg[i].score = 0; beg[i].qb = beg[i].tb = -1; }
 		if (sb) { sub[i].score2 = 0; sub[i].qe2 = sub[i].te2 = -1; }
-		if (ql <= 0 || tl <= 0 || smax <= 0) continue;          /* nothing scores above 0: no launch */
+		if (ql <= 0 || tl <= 0 || (!ft && smax <= 0)) continue;          /* nothing scores above 0 (ft: a corner result): no launch */
 		s.rows = imax(ql, tl); s.cols = imin(ql, tl); s.sw = ql > tl; s.idx = (uint32_t)i;
-		if (sb) { s.rows = tl; s.cols = ql; s.sw = 0; }          /* row maxima are per target position only if rows = target */
+		if (sb || ft) { s.rows = tl; s.cols = ql; s.sw = 0; }    /* row maxima (ft: the last column) are per target position only if rows = target */
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
-		if (form > 0 && ll_pk_admit(ql, tl, smax) && s.cols <= 65535) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
+		if (form > 0 && (ft ? ll_sg_pk_admit(ql, gapo, gape, smax) : ll_pk_admit(ql, tl, smax) && s.cols <= 65535)) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
 		else i32[ni32++] = s;
 	}
 	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
@@ -162,7 +194,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] %s-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers", sb->excl,
 	                              du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
-	if (ntk == 0 && !flat) { free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
+	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, res); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
@@ -247,7 +279,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 			rc = fail(KSW2AMD_E_PARAM, "local alignment: pair %s: residue code >= m", msg);
 			goto out;
 		}
-		if (ntk == 0) goto out;
+		if (ntk == 0) goto done;
 	}
 	{
 		K2aLL par;
@@ -275,6 +307,8 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		for (i = 0; i < npk; ++i) memcpy(&sub[pk[i].idx], &hs[pk[i].idx], sizeof(K2aLLSub));       /* ksw2amd_lsub_t is K2aLLSub */
 		for (i = 0; i < ni32; ++i) memcpy(&sub[i32[i].idx], &hs[i32[i].idx], sizeof(K2aLLSub));
 	}
+done:
+	if (ft) ll_fit_corners(src, n, gapo, gape, res);
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);
@@ -289,28 +323,31 @@ out:
 /* ksw2amd_ll_batch (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch (ksw2_host_lla.c), and ksw2amd_ll_sub_batch (ksw2_host_lls.c);
  * du: their two-piece forms, sb with du included (ksw2_host_lld.c, ksw2_host_llds.c) */
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
+                const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du, const ll_fit_t *ft)
 {
-	int i, rc, beg = 0, smax = -128;
+	int i, rc, beg = 0, smax = -128, any = 0;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs) || (sb && !subs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
+	if (ft) smax = imax(smax, 0);
 	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */
 		const ksw2amd_lpair_t *p = &pairs[i];
 		char msg[96];
 		if ((p->qlen > 0 && !p->query) || (p->tlen > 0 && !p->target)) { snprintf(msg, sizeof(msg), "%d", i); return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: NULL sequence", msg); }
+		if (ft && (rc = ll_sg_check_range(i, p->qlen, gapo, gape, smax)) != KSW2AMD_OK) return rc;
 		if ((p->qlen > 0 && ll_bad_code(p->query, p->qlen, m)) || (p->tlen > 0 && ll_bad_code(p->target, p->tlen, m))) {
 			snprintf(msg, sizeof(msg), "%d", i);
 			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: residue code >= m", msg);
 		}
+		any |= p->qlen > 0 && p->tlen > 0;
 	}
-	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
 	if (n == 0) return KSW2AMD_OK;
-	if (smax > 0 && k2a_shim_device_count() <= 0) return fail(KSW2AMD_E_NODEVICE, "no usable %s device", k2a_shim_backend());
+	if ((ft ? any : smax > 0) && k2a_shim_device_count() <= 0) return fail(KSW2AMD_E_NODEVICE, "no usable %s device", k2a_shim_backend());
 	while (beg < n) {                                       /* chunks of up to ~3 GB of arena + boundary scratch */
 		size_t b = 0;
 		int end;
 		for (end = beg; end < n; ++end) {
-			const size_t pb = ll_pair_bytes(pairs[end].qlen, pairs[end].tlen, sb != 0, du != 0);
+			const size_t pb = ll_pair_bytes(pairs[end].qlen, pairs[end].tlen, sb != 0, du != 0, ft != 0);
 			if (end > beg && (b + pb > 3000000000u || end - beg >= (1 << 22))) break;
 			b += pb;
 		}
@@ -318,7 +355,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 			ll_src_t src;
 			memset(&src, 0, sizeof(src));
 			src.pairs = pairs + beg;
-			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du);
+			rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du, ft);
 		}
 		if (rc) return rc;
 		beg = end;
@@ -328,7 +365,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 
 int ksw2amd_ll_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
 {
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, 0);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, 0, 0);
 }
 
 /* ---------------------------------------------------------------- ksw_ll_qinit / ksw_ll_i16 (ksw2.h:92-93) */

@@ -90,7 +90,7 @@ int lla_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int fla
 		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
-	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, rev, beg, 0, 0, du)) != KSW2AMD_OK) goto out;
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, rev, beg, 0, 0, du, 0)) != KSW2AMD_OK) goto out;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
 	rc = lla_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln, du);

@@ -27,14 +27,14 @@ int ksw2amd_lld_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, i
 {
 	ll_dual_t du;
 	lld_dual(&du, gapo2, gape2);
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, &du);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, &du, 0);
 }
 
 int ksw2amd_lld_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res)
 {
 	ll_dual_t du;
 	lld_dual(&du, gapo2, gape2);
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, &du);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, &du, 0);
 }
 
 int ksw2amd_lld_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lpair_t *pairs,

@@ -27,7 +27,7 @@ int ksw2amd_lld_sub_batch(int m, const int8_t *mat, int gapo, int gape, int gapo
 	ll_dual_t du;
 	int rc;
 	if ((rc = llds_setup(m, mat, gapo, gape, gapo2, gape2, excl, &sb, &du)) != KSW2AMD_OK) return rc;
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, &sb, sub, &du);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, &sb, sub, &du, 0);
 }
 
 int ksw2amd_lld_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int excl, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res,
@@ -37,7 +37,7 @@ int ksw2amd_lld_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int
 	ll_dual_t du;
 	int rc;
 	if ((rc = llds_setup(m, mat, gapo, gape, gapo2, gape2, excl, &sb, &du)) != KSW2AMD_OK) return rc;
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, &sb, sub, &du);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, &sb, sub, &du, 0);
 }
 
 int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int excl, int *qe, int *te, ksw2amd_lsub_t *sub)

@@ -32,7 +32,7 @@ static int llf_pair_span(const ksw2amd_lflat_t *in, int i, uint64_t *lo, uint64_
 /* ksw2amd_ll_batch_flat (rev = 0, sb = 0), the first two stages of ksw2amd_ll_align_batch_flat, and ksw2amd_ll_sub_batch_flat (sb); du: their
  * two-piece forms, sb with du included */
 int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
-                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du)
+                 const ll_sub_t *sb, ksw2amd_lsub_t *subs, const ll_dual_t *du, const ll_fit_t *ft)
 {
 	const size_t limit = llf_chunk_bytes();
 	int i, rc, beg = 0, smax = -128;
@@ -40,6 +40,8 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || !in || (n > 0 && (!in->base || !in->qoff || !in->toff || !in->qlen || !in->tlen || !res || (rev && !begs) || (sb && !subs))))
 		return fail(KSW2AMD_E_PARAM, "local alignment: bad flat batch arguments%s", "");
+	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
+	if (ft) smax = imax(smax, 0);
 	for (i = 0; i < n; ++i) {                              /* every argument before anything is uploaded */
 		uint64_t lo, hi;
 		res[i].score = 0; res[i].qe = res[i].te = -1;       /* a failing chunk leaves the later ones at their reset values */
@@ -49,8 +51,8 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 			snprintf(msg, sizeof(msg), "%d", i);
 			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: query and target lie more than 4 GiB apart in the arena", msg);
 		}
+		if (ft && (rc = ll_sg_check_range(i, in->qlen[i], gapo, gape, smax)) != KSW2AMD_OK) return rc;
 	}
-	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
 	if (n == 0) return KSW2AMD_OK;
 	if (k2a_shim_device_count() <= 0) return fail(KSW2AMD_E_NODEVICE, "no usable %s device", k2a_shim_backend());      /* the check runs there whatever the matrix */
 	while (beg < n) {                                       /* chunks: pairs in order while the span and the bytes stay under the limit */
@@ -59,7 +61,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 		uint64_t clo = 0, chi = 0;
 		int end, any = 0;
 		for (end = beg; end < n; ++end) {
-			const size_t pb = ll_pair_bytes(in->qlen[end], in->tlen[end], sb != 0, du != 0) + 2 * sizeof(K2aLLChk);
+			const size_t pb = ll_pair_bytes(in->qlen[end], in->tlen[end], sb != 0, du != 0, ft != 0) + 2 * sizeof(K2aLLChk);
 			uint64_t lo, hi, nlo = clo, nhi = chi;
 			if (llf_pair_span(in, end, &lo, &hi)) { nlo = any && clo < lo ? clo : lo; nhi = any && chi > hi ? chi : hi; }
 			if (end > beg && (b + pb > limit || nhi - nlo > limit || nhi - nlo > LLF_SPAN_MAX || end - beg >= (1 << 22))) break;
@@ -69,7 +71,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 		}
 		memset(&src, 0, sizeof(src));
 		src.flat = in; src.first = beg; src.lo = clo; src.hi = chi; src.check = k2a_shim_launch_ll_check;
-		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du);
+		rc = ll_chunk(m, mat, smax, gapo, gape, end - beg, &src, res + beg, rev, rev ? begs + beg : 0, sb, sb ? subs + beg : 0, du, ft);
 		if (rc) return rc;
 		beg = end;
 	}
@@ -78,7 +80,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 
 int ksw2amd_ll_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res)
 {
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, 0);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, 0, 0);
 }
 
 int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln, ll_rev_fn rev,
@@ -97,7 +99,7 @@ int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int fla
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "local alignment: host allocation failed%s", ""); goto out; }
 	}
 	/* stages 1 and 2 on the borrowed arena */
-	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, rev, beg, 0, 0, du)) != KSW2AMD_OK) goto reset;
+	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, rev, beg, 0, 0, du, 0)) != KSW2AMD_OK) goto reset;
 	if ((rc = lla_cells(n, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if ((flag & KSW_EZ_SCORE_ONLY) || na == 0) goto out;
 	/* stage 3: the intervals [qoff + qb, qoff + qe] x [toff + tb, toff + te] under the scalar ksw_extz (du: ksw_extd) contract.  Host arena: pointers

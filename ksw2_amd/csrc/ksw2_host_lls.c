@@ -22,7 +22,7 @@ int ksw2amd_ll_sub_batch(int m, const int8_t *mat, int gapo, int gape, int excl,
 	int rc;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (rc = lls_check_excl(excl)) != KSW2AMD_OK) return rc;
 	sb.launch = k2a_shim_launch_ll_sub; sb.excl = excl;
-	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, &sb, sub, 0);
+	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, &sb, sub, 0, 0);
 }
 
 int ksw2amd_ll_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int excl, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res, ksw2amd_lsub_t *sub)
@@ -31,7 +31,7 @@ int ksw2amd_ll_sub_batch_flat(int m, const int8_t *mat, int gapo, int gape, int 
 	int rc;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (rc = lls_check_excl(excl)) != KSW2AMD_OK) return rc;
 	sb.launch = k2a_shim_launch_ll_sub; sb.excl = excl;
-	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, &sb, sub, 0);
+	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, &sb, sub, 0, 0);
 }
 
 int ksw2amd_ll_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape, int excl, int *qe, int *te, ksw2amd_lsub_t *sub)

@@ -101,12 +101,20 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * length l: a second pair of gap states E2 / F2 under (oe2, ge2) beside E / F, clamped at 0 like them (max(0, .., max(X, 0)) = max(0, .., X),
  * and max(H - oe, max(X, 0) - ge, 0) = max(max(H - oe, X - ge), 0) because -ge <= 0: H never sees the clamp), f2[] per row and
  * an e2 chain down the strip that reaches the lane below (and the boundary) with H and E.  With DUAL = false nothing of it exists. */
-template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false>
+/* FIT (rows = target, never with REV / SUB / DUAL): the semi-global mode of ksw2amd_sg_batch -- the whole query
+ * against the best interval of the target, no clamp at 0.  With B = gapo + ncols * gape every true H(t, j) >= -(gapo + (j + 1) * gape) >= -B
+ * (insert the query up to column j), so the cell update runs unchanged on H' = H + B >= 0; E' and F' held clamped at 0 stand for values
+ * <= -B, which reach an H only where H = -B itself.  What differs is the boundary -- column -1 is B in every row (H(t, -1) = 0), row -1 is
+ * B - (gapo + (j + 1) * gape) = (ncols - 1 - j) * gape (fit_top) -- and the maximum: it is taken over the last column only, which is what
+ * hl[] holds when a lane has walked its columns, so step() keeps no row maximum at all and gen_end folds hl[] into (largest H', smallest
+ * row).  The key starts at -1, below any H'; the score is H' - B. */
+template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
 	int nrows, ncols, swapped, m, lane, i0;
 	uint32_t smax, oe, ge;                     /* packed: the value in both halves */
 	uint32_t oe2, ge2;                         /* DUAL: the second piece */
+	uint32_t bias;                             /* FIT: B, in both halves when packed */
 	uint32_t hu_prev;                          /* H(i0 - 1, jj - 1): what the lane above delivered one step earlier */
 	uint32_t hl[C], f[C], rmax[C], rcol[C];    /* H(i, jj - 1), F(i, jj), row maximum and its first column */
 	uint32_t f2[DUAL ? C : 1];                 /* DUAL: F2(i, jj) */
@@ -132,13 +140,26 @@ struct K2aLaneLL {
 		smax = (uint32_t)par.smax * x; oe = (uint32_t)par.oe * x; ge = (uint32_t)par.ge * x;
 		if (DUAL) { oe2 = (uint32_t)par.oe2 * x; ge2 = (uint32_t)par.ge2 * x; }
 		for (int h = 0; h < NH; ++h) k2a_ll_key_reset(key[h]);
+		if (FIT) {
+			bias = (uint32_t)(par.oe - par.ge + ncols * par.ge) * x;
+			for (int h = 0; h < NH; ++h) key[h].s = -1;
+		}
+	}
+
+	/* FIT: B, and row -1 of column k for lane 0 of the first generation: H'(-1, k) and E'(0, k) = sat(H'(-1, k) - oe) */
+	K2A_FN int fit_bias() const { return (int)(bias & (PK ? 0xffffu : 0xffffffffu)); }
+	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e) const
+	{
+		const int v = (ncols - 1 - k) * (int)(ge & (PK ? 0xffffu : 0xffffffffu)), w = k2a_max(v - (int)(oe & (PK ? 0xffffu : 0xffffffffu)), 0);
+		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u);
 	}
 
 	/* start generation g: this lane's rows, their profile, zeroed columns (tab = the task's pen table in LDS, [row code * m + column code]) */
 	K2A_FN void gen_begin(int g, const uint8_t *r0, const uint8_t *r1, const uint8_t *tab)
 	{
 		i0 = g * K2A_LL_ROWS + lane * C;
-		hu_prev = 0;
+		hu_prev = FIT ? bias : 0u;
+		const uint32_t f0 = !FIT ? 0u : PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);      /* FIT: F'(i, 0) = sat(B - oe) */
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			const int i = i0 + c;
@@ -149,7 +170,7 @@ struct K2aLaneLL {
 			} else {
 				a = i < nrows ? r0[i] : 0u; b = (PK && i < nrows) ? r1[i] : 0u;
 			}
-			hl[c] = 0; f[c] = 0; rmax[c] = 0; rcol[c] = 0;
+			hl[c] = FIT ? bias : 0u; f[c] = f0; rmax[c] = 0; rcol[c] = 0;
 			if (DUAL) f2[DUAL ? c : 0] = 0;
 			if (LDSP) {
 				pa[c] = a * (uint32_t)m;
@@ -209,11 +230,13 @@ struct K2aLaneLL {
 					e2 = k2a_ll_max(hoe2, k2a_ll_subs(e2, ge2));
 					f2[DUAL ? c : 0] = k2a_ll_max(hoe2, k2a_ll_subs(f2[DUAL ? c : 0], ge2));
 				}
-				const uint32_t hm = (REV && PK) ? h & cmask : h;                      /* REV: 0 in a half whose rectangle ends before jj */
-				const uint32_t d = k2a_ll_subs(hm, rmax[c]);                          /* > 0 in a half where h is a new row maximum */
-				const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
-				rmax[c] = k2a_ll_max(rmax[c], hm);
-				rcol[c] = (jj2 & mask) | (rcol[c] & ~mask);
+				if (!FIT) {
+					const uint32_t hm = (REV && PK) ? h & cmask : h;                  /* REV: 0 in a half whose rectangle ends before jj */
+					const uint32_t d = k2a_ll_subs(hm, rmax[c]);                      /* > 0 in a half where h is a new row maximum */
+					const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
+					rmax[c] = k2a_ll_max(rmax[c], hm);
+					rcol[c] = (jj2 & mask) | (rcol[c] & ~mask);
+				}
 			} else {
 				const int t = (int)hd + (int)smax - (int)pen;                          /* e, f >= 0: h >= 0 without a clamp */
 				int hi = k2a_max(k2a_max(t, (int)e), (int)f[c]);
@@ -227,7 +250,7 @@ struct K2aLaneLL {
 					f2[DUAL ? c : 0] = (uint32_t)k2a_max3(hoe2, (int)f2[DUAL ? c : 0] - (int)ge2, 0);
 				}
 				h = (uint32_t)hi;
-				if (hi > (int)rmax[c]) { rmax[c] = h; rcol[c] = jj2; }
+				if (!FIT && hi > (int)rmax[c]) { rmax[c] = h; rcol[c] = jj2; }
 			}
 			hd = hl[c];
 			hl[c] = h;
@@ -246,10 +269,11 @@ struct K2aLaneLL {
 			const int i = i0 + c;
 #pragma unroll
 			for (int h = 0; h < NH; ++h) {
-				const int s = (int)(PK ? (rmax[c] >> (16 * h)) & 0xffffu : rmax[c]);
-				const int j = (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
+				const uint32_t rm = FIT ? hl[c] : rmax[c];                            /* FIT: H'(i, ncols - 1), the row's last column */
+				const int s = (int)(PK ? (rm >> (16 * h)) & 0xffffu : rm);
+				const int j = FIT ? ncols - 1 : (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
 				const int te = swapped ? j : i, qe = swapped ? i : j;
-				const bool take = i < (REV ? rl[REV ? h : 0] : nrows) && s > 0 && k2a_ll_better(s, te, qe, key[h]);
+				const bool take = i < (REV ? rl[REV ? h : 0] : nrows) && (FIT || s > 0) && k2a_ll_better(s, te, qe, key[h]);
 				key[h].s = take ? s : key[h].s;
 				key[h].te = take ? te : key[h].te;
 				key[h].qe = take ? qe : key[h].qe;

@@ -205,6 +205,12 @@ int k2a_shim_launch_ll_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *t
  * the reduction of k2a_shim_launch_ll_sub as it is.  Only ksw2_host_llds.c calls it (the other simulator builds have no such symbol). */
 int k2a_shim_launch_lld_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                             uint8_t *scratch, K2aLLRes *res, uint8_t *prof, int excl, K2aLLSub *sub, void *stream);
+/* ksw2amd_sg_batch: the semi-global mode on the task table of k2a_shim_launch_ll with rows = target
+ * (tasks[].swapped = 0) and par->smax = max(0, largest entry): H' = H + gapo + ncols * gape through the same cell update, the free
+ * start in the target and the inserted query prefix as boundary values, the maximum over the last column.  res[slot] = (score, ncols - 1,
+ * te), the smallest te on a tie.  Only ksw2_host_sg.c calls it (the other simulator builds have no such symbol). */
+int k2a_shim_launch_sg(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2191,8 +2191,10 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * both scored 0 runs none.  beg[tk.res[h]] = score of the pass, qb, tb.
  * DUAL (k2a_lld_kernel / k2a_lld_rev_kernel): the two-piece gap cost.  E2 travels with H and E: one more rotate
  * per step, and a boundary entry of 16 bytes per column (H, E, E2, pad) stored and prefetched as one access.
- * SUB (k2a_ll_fsub_kernel; with DUAL: k2a_lld_fsub_kernel): the forward pass that also streams every generation's row maxima to `prof`. */
-template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false>
+ * SUB (k2a_ll_fsub_kernel; with DUAL: k2a_lld_fsub_kernel): the forward pass that also streams every generation's row maxima to `prof`.
+ * FIT (k2a_sg_kernel): the semi-global mode on biased values.  Rows are the target; lane 0 of the first generation
+ * takes row -1 from K2aLaneLL::fit_top instead of zeros, and the score leaves the bias behind. */
+template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
             uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg,
@@ -2211,7 +2213,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
 	uint2 *bnd = (uint2*)(scratch + tk.boff);
 	uint4 *bnd2 = (uint4*)(scratch + tk.boff);        /* DUAL: the host sized and aligned the boundary for 16 bytes per column */
-	K2aLaneLL<PK, LDSP, REV, SUB, DUAL> L;
+	K2aLaneLL<PK, LDSP, REV, SUB, DUAL, FIT> L;
 	L.init(par, tk, lane);
 	int fq[2] = { 0, 0 }, ft[2] = { 0, 0 };        /* REV: the forward end cells */
 	if (REV) {
@@ -2248,7 +2250,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 			if (lane == 0 && from_bnd) {
 				if (DUAL) { const uint4 v = bnd2[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; e2 = v.z; }
 				else { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
-			}
+			} else if (FIT && lane == 0) L.fit_top(k2a_min(k, ncols - 1), h, e);
 		};
 		uint32_t unused2 = 0;
 #pragma unroll
@@ -2296,7 +2298,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 				K2aLLBeg b; b.score = k.s; b.qb = pos ? fq[h] - k.qe : -1; b.tb = pos ? ft[h] - k.te : -1;
 				beg[tk.res[h]] = b;
 			} else {
-				K2aLLRes r; r.score = k.s; r.qe = k.qe; r.te = k.te;
+				K2aLLRes r; r.score = FIT ? k.s - L.fit_bias() : k.s; r.qe = k.qe; r.te = k.te;
 				res[tk.res[h]] = r;
 			}
 		}
@@ -2317,6 +2319,15 @@ k2a_ll_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntas
                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	k2a_ll_task<PK, LDSP, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+/* semi-global alignment (ksw2amd_sg_batch): the whole query in the best interval of the target */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_sg_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+              uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false, false, false, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
 }
 
 /* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
@@ -2861,6 +2872,22 @@ int k2a_shim_launch_ll(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
 	else if (pk) hipLaunchKernelGGL((k2a_ll_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else if (lds) hipLaunchKernelGGL((k2a_ll_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else hipLaunchKernelGGL((k2a_ll_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* semi-global alignment: the four forms of k2a_shim_launch_ll on tasks whose rows are the target; par->smax is max(0, largest entry) */
+int k2a_shim_launch_sg(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "semi-global alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_sg_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (pk) hipLaunchKernelGGL((k2a_sg_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (lds) hipLaunchKernelGGL((k2a_sg_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_sg_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -47,7 +47,15 @@ and of k2a_lld_kernel (+ k2a_lld_rev_kernel), their ratio and the batch-to-batch
 --dual --sub: ksw2amd_lld_sub_batch beside ksw2amd_lld_batch, both under (4, 2, 24, 1), on the same prebuilt pair
 array, the library call alone in the clock on both sides; pairs/s and GCUPS of both and their ratio, the forms both took, res equality and
 a parity sample against tests/llds_oracle.c.  --ktrace: per batch the time of k2a_lld_kernel, of k2a_lld_fsub_kernel and of
-k2a_ll_sub_kernel, the ratio (k2a_lld_fsub_kernel + k2a_ll_sub_kernel) / k2a_lld_kernel and the batch-to-batch spread of k2a_lld_kernel."""
+k2a_ll_sub_kernel, the ratio (k2a_lld_fsub_kernel + k2a_ll_sub_kernel) / k2a_lld_kernel and the batch-to-batch spread of k2a_lld_kernel.
+
+  python tools/scripts/ll_bench.py --workload A --sg [--ktrace kernel_trace.csv] [--out profiles/sg_bench_A.json]
+
+--sg: ksw2amd_sg_batch (semi-global) beside ksw2amd_ll_batch on the same prebuilt pair array, every pair oriented so
+that its target is the longer sequence (both entries then run it with rows = target), the library call alone in the clock on both sides
+and the two entries ALTERNATING batch by batch in one process; pairs/s and GCUPS (qlen x tlen cells) of both, their ratio, the spread of
+the ll_batch batches, the forms both took and a parity sample against tests/sg_oracle.c.  --ktrace: per batch the time of k2a_ll_kernel
+and of k2a_sg_kernel, their ratio and the batch-to-batch spread of k2a_ll_kernel."""
 import argparse
 import ctypes
 import csv
@@ -291,6 +299,71 @@ def main_sub(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["res_equal"] and rec["parity_ok"] else 1
 
 
+def main_sg(a, lib, q, t, mat, gapo, gape, cells, form):
+    from tests import sg_util as sg
+    swap = [len(x) > len(y) for x, y in zip(q, t)]
+    q, t = [y if w else x for x, y, w in zip(q, t, swap)], [x if w else y for x, y, w in zip(q, t, swap)]      # target >= query
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res, res2 = (np.zeros((n, 3), dtype=np.int32) for _ in range(2))
+    rp = lambda x, ty: x.ctypes.data_as(ctypes.POINTER(ty))
+    fns = dict(ll_batch=lambda: L.ksw2amd_ll_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(res, ksw2_amd.LocalResult)),
+               sg_batch=lambda: L.ksw2amd_sg_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(res2, ksw2_amd.LocalResult)))
+    tags = dict(ll_batch="ll: pairs", sg_batch="sg: pairs")
+    forms = {}
+    os.environ["KSW2AMD_TRACE"] = "1"                          # the warm-ups' form lines
+    for name, fn in fns.items():
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            forms[name] = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tags[name] in l]
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+    os.environ.pop("KSW2AMD_TRACE")                            # (the binding re-reads the environment in front of every call)
+    times = dict(ll_batch=[], sg_batch=[])
+    for _ in range(a.reps):                                    # alternating: ll, sg, ll, sg, ...
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    rec = dict(workload=a.workload, mode="sg", pairs=n, cells=cells, ll_form=form, pairs_turned_round=int(sum(swap)),
+               clock="library call only: the pair array is built before it; the two entries alternate batch by batch")
+    for name in fns:
+        ts = times[name]
+        rec[name] = dict(e2e_s=min(ts), e2e_all_s=ts, pairs_per_s=n / min(ts), e2e_gcups=cells / min(ts) / 1e9, forms=forms[name])
+    rec["sg_over_ll_e2e"] = rec["sg_batch"]["e2e_s"] / rec["ll_batch"]["e2e_s"]
+    rec["ll_e2e_spread"] = (max(times["ll_batch"]) - min(times["ll_batch"])) / min(times["ll_batch"])
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = sg.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, gapo, gape, 5)
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool((res2[idx] == exp).all())
+    rec["negative_scores"] = int((res2[:, 0] < 0).sum())
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        kl = trace_batches(a.ktrace, "k2a_ll_kernel", nl(forms["ll_batch"][0]))[1:]        # [0]: the warm-up
+        ks = trace_batches(a.ktrace, "k2a_sg_kernel", nl(forms["sg_batch"][0]))[1:]
+        rec["kernel"] = dict(ll_kernel_ms=kl, sg_kernel_ms=ks,
+                             ll_kernel_spread=(max(kl) - min(kl)) / min(kl) if kl else None,
+                             sg_over_ll=(sum(ks) / len(ks)) / (sum(kl) / len(kl)) if kl and ks else None,
+                             ll_resident_gcups=cells / (sum(kl) / len(kl) * 1e-3) / 1e9 if kl else None,
+                             sg_resident_gcups=cells / (sum(ks) / len(ks) * 1e-3) / 1e9 if ks else None)
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] else 1
+
+
 def main_dual(a, lib, q, t, mat, gapo, gape, cells, form):
     from tests import lld_util as ld
     n = len(q)
@@ -460,6 +533,7 @@ def main():
                     help="ksw2amd_ll_batch_flat / _align_batch_flat from one arena against the pointer entry, library calls only in the clock")
     ap.add_argument("--sub", action="store_true", help="ksw2amd_ll_sub_batch beside ksw2amd_ll_batch on the same pair array, library calls only in the clock")
     ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries; with --sub ksw2amd_lld_sub_batch beside ksw2amd_lld_batch")
+    ap.add_argument("--sg", action="store_true", help="ksw2amd_sg_batch beside ksw2amd_ll_batch on the same pair array (target >= query), alternating, library calls only in the clock")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -476,6 +550,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.sg:
+        return main_sg(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.dual and a.sub:
         return main_dual_sub(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.dual:
