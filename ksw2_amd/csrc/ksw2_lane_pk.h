@@ -394,7 +394,10 @@ struct K2aLanePk {
 
 	/* bsA / bsB: bases of the lane that owns the strip above (RB only; rotated in by the kernel) */
 	/* forced (k2a_argmax_kernel): the strip's bases and first diagonal input come from its checkpoint header instead of the lane above */
-	K2A_FN void do_init(const K2aScoring &sc, int bsA = 0, int bsB = 0, const K2aCkHead *forced = 0)
+	/* col0_any (k2a_fill_pk_body, COL0U): false = no lane that starts a strip at this step has rows at column 0 (i0 <= w), this one
+	 * included; the kernel passes the lanes' common answer, so the border rows below sit behind one scalar branch */
+	template<bool COL0U = false>
+	K2A_FN void do_init(const K2aScoring &sc, int bsA = 0, int bsB = 0, const K2aCkHead *forced = 0, bool col0_any = true)
 	{
 		S = Snext; i0 = S * C; koff = koff_next;
 		je = k2a_min(qlen - 1, k2a_min(i0 + C - 1, tlen - 1) + w);
@@ -438,14 +441,19 @@ struct K2aLanePk {
 			delta = S == 0 ? 0u : k2a_pair16((uint32_t)(bsA - nbA) & 0xffffu, (uint32_t)(bsB - nbB) & 0xffffu);
 			baseA = nbA; baseB = nbB;
 		}
-		if (i0 <= w) {                                          /* some rows start at column 0: virtual column -1 */
+		if (col0_any) {
+			/* (the fence pins this block: without it hipcc folds the flag into each row's own guard below, and the C guards run
+			 * again at every strip start) */
+			if (COL0U) K2A_SCHED_FENCE();
+			if (i0 <= w) {                                      /* some rows start at column 0: virtual column -1 */
 #pragma unroll
-			for (int c = 0; c < C; ++c) {                        /* ksw2_extz.c:43-44, ksw2_extd.c:49-52; row bias e*i */
-				const int hb = k2a_border<DUAL>(sc, i0 + c + 1) + sc.e * (i0 + c);
-				if (i0 + c <= w) {
-					hl[c] = k2a_ofs_on(k2a_pair16((uint32_t)(hb - baseA) & 0xffffu, (uint32_t)(hb - baseB) & 0xffffu));
-					f[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e));
-					if (DUAL) f2[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2));
+				for (int c = 0; c < C; ++c) {                    /* ksw2_extz.c:43-44, ksw2_extd.c:49-52; row bias e*i */
+					const int hb = k2a_border<DUAL>(sc, i0 + c + 1) + sc.e * (i0 + c);
+					if (i0 + c <= w) {
+						hl[c] = k2a_ofs_on(k2a_pair16((uint32_t)(hb - baseA) & 0xffffu, (uint32_t)(hb - baseB) & 0xffffu));
+						f[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e));
+						if (DUAL) f2[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2));
+					}
 				}
 			}
 		}

@@ -59,17 +59,33 @@ __device__ __forceinline__ int k2a_wave_id()
 	return UNIFORM ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
 }
 
+/* Build switches of the packed fill's strip events and step preamble, default on; =0 builds the earlier form, for A/B libraries
+ * (tools/scripts/ab_libs.sh), in the style of K2A_UNIFORM_ROWMASK below.
+ * K2A_STEP_TRIM: the rotates leave the DPP destination uninitialised, and the deferred single-group fill has no early-stop test.
+ *   (The rotate, k2a_rot1, is every kernel's: a K2A_STEP_TRIM=0 library differs from the default one in all of them, by the v_mov that
+ *   zeroes the destination in front of each rotate.  Results are the same either way.)
+ * K2A_INIT_COL0_UNIFORM: the column-0 border rows of K2aLanePk::do_init sit behind one wavefront-uniform branch. */
+#ifndef K2A_STEP_TRIM
+#define K2A_STEP_TRIM 1
+#endif
+#ifndef K2A_INIT_COL0_UNIFORM
+#define K2A_INIT_COL0_UNIFORM 1
+#endif
+
 template<int G>
 __device__ __forceinline__ int k2a_rot1(int v)
 {
-	/* lane l <- lane l-1 inside its group (lane 0 <- lane G-1) */
-	if (G == 64) return __builtin_amdgcn_update_dpp(0, v, 0x13C /* wave_ror:1 */, 0xf, 0xf, false);
-	else if (G == 16) return __builtin_amdgcn_update_dpp(0, v, 0x121 /* row_ror:1  */, 0xf, 0xf, false);
+	/* lane l <- lane l-1 inside its group (lane 0 <- lane G-1).  Every lane has a source under these controls (a rotate, full row and
+	 * bank masks), so the "old" value of the destination is never kept: with bound_ctrl set the compiler knows that and drops the
+	 * v_mov_b32 that would zero the destination in front of every v_mov_b32_dpp (same result: an absent source would read as 0). */
+	constexpr bool BC = K2A_STEP_TRIM != 0;
+	if (G == 64) return __builtin_amdgcn_update_dpp(0, v, 0x13C /* wave_ror:1 */, 0xf, 0xf, BC);
+	else if (G == 16) return __builtin_amdgcn_update_dpp(0, v, 0x121 /* row_ror:1  */, 0xf, 0xf, BC);
 	else {
 		/* G == 8: two groups per 16-lane row.  row_shr:1 serves lanes 1..7 and 9..15; lanes 0 and 8 take lanes 7 and 15,
 		 * which row_ror:9 delivers (lane l <- lane (l-9) mod 16). */
 		const int shifted = __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-		const int wrapped = __builtin_amdgcn_update_dpp(0, v, 0x129 /* row_ror:9 */, 0xf, 0xf, false);
+		const int wrapped = __builtin_amdgcn_update_dpp(0, v, 0x129 /* row_ror:9 */, 0xf, 0xf, BC);
 		return (threadIdx.x & 7) == 0 ? wrapped : shifted;
 	}
 }
@@ -378,6 +394,15 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	const size_t tbsteps = (size_t)(klast + 1);
 	uint8_t *tbp = tb + prA.tb_off;
 	constexpr bool UMASK = K2A_UNIFORM_ROWMASK != 0 && MODE == K2A_MODE_SCORE;
+	constexpr bool COL0U = K2A_INIT_COL0_UNIFORM != 0;
+	/* The early-stop test at the bottom of a step, "no lane with gdone clear and k < klast", cannot fire before the loop's own bound
+	 * in a deferred fill of one group per wavefront (DEFER, NG == 1): gdone stays what it starts as, !valid (only the non-deferred
+	 * epilogue sets it), `valid` is one task's and so the same in all 64 lanes, and so is klast (last_step() reads the task's
+	 * lengths, band and strip count only), hence klast == kmax in every lane.  A valid wavefront: the ballot is non-zero for every
+	 * k < kmax, and at k == kmax the loops end by their bounds anyway (kge <= kmax; kg + 4 > kmax), with the same assignments behind
+	 * the inner loop.  An all-invalid wavefront: klast = kmax = -1 and the loop is never entered.  So the test is compiled out
+	 * there: two v_readlane, a select, a compare and the scalar registers of klast and gdone per step. */
+	constexpr bool NOSTOP = K2A_STEP_TRIM != 0 && DEFER && NG == 1;
 	K2aRowMasks<C> RM;
 	RM.reset();
 	Stage ST;
@@ -407,10 +432,14 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 
 		const bool ninit = L.need_init(k);
 		const uint64_t initmask = __builtin_amdgcn_ballot_w64(ninit);
+		uint64_t col0mask = 0;                                  /* the lanes whose new strip has rows that start at column 0 (i0 <= w) */
 		if (initmask != 0) {
 			const int bsA = RB ? k2a_rot1<G>(L.baseA) : 0, bsB = RB ? k2a_rot1<G>(L.baseB) : 0;
+			/* do_init sets i0 = Snext * C.  Only the first (w + 1) / C + 1 strips of an alignment have such rows: the lanes'
+			 * common answer keeps do_init's C guarded border rows behind one scalar branch for all the others */
+			if (UMASK || COL0U) col0mask = __builtin_amdgcn_ballot_w64(ninit && L.Snext * C <= L.w);
 			if (ninit) {
-				L.do_init(sc, bsA, bsB);                          /* uses hu_prev = what arrived one step ago */
+				L.template do_init<COL0U>(sc, bsA, bsB, 0, COL0U ? col0mask != 0 : true);      /* uses hu_prev = what arrived one step ago */
 				if (k & 3) L.reload_query_group(k);                /* the group was fetched under the previous strip's offset */
 				if (ckon) { K2aCkHead h; h.baseA = L.baseA; h.baseB = L.baseB; h.hd0 = L.hd0; h.pad = 0; ckhd[L.S] = h; }
 			}
@@ -418,7 +447,7 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 		}
 		if (UMASK) {
 			/* a last, partial strip (rows that do not exist) or a strip at column 0 (rows 0 .. w - i0 live at once): refresh below */
-			if (initmask != 0) RM.on_init(initmask, __builtin_amdgcn_ballot_w64(ninit && L.rows_m1 != C - 1), __builtin_amdgcn_ballot_w64(ninit && L.i0 <= L.w));
+			if (initmask != 0) RM.on_init(initmask, __builtin_amdgcn_ballot_w64(ninit && L.rows_m1 != C - 1), col0mask);
 			const int dd = k - L.kd;
 			RM.advance(__builtin_amdgcn_ballot_w64((uint32_t)(dd + L.w) <= (uint32_t)(2 * L.w)));
 			if (RM.needs_refresh()) {
@@ -475,7 +504,7 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 			}
 			if (TN && L.wn) K2A_SYNC_WN(L);
 		}
-		if (zseq && __builtin_amdgcn_ballot_w64(!(gdone || k >= klast)) == 0) { stop = true; break; }   /* only a Z-drop ends a group early */
+		if (!NOSTOP && zseq && __builtin_amdgcn_ballot_w64(!(gdone || k >= klast)) == 0) { stop = true; break; }   /* only a Z-drop ends a group early */
 	}
 	L.qwA = qpa; L.qwB = qpb;
 	}
