@@ -430,13 +430,45 @@ int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape
  * without a positive entry is legal here (the local entries skip such pairs; these do not).  Every argument and every code is checked
  * before anything is staged or launched (KSW2AMD_E_PARAM); the flat entry checks the codes on the device, chunk by chunk, and has the
  * chunking, reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat.
- * Not computed: the start tb of the interval and a CIGAR, the two-piece gap cost, free query ends.
+ * Not computed: the two-piece gap cost, free query ends, a suboptimal score (the start tb and a CIGAR: ksw2amd_sg_align_batch below).
  * ksw2amd_sg: one pair on a ksw_ll_qinit profile; returns the score, equal to row 0 of ksw2amd_sg_batch on that pair.  On a device
  * failure or a bad argument it returns 0 with *qe = *te = -1 and reports like ksw_ll_i16 (ksw2amd_error_count, ksw2amd_last_error, the
  * handler, KSW2AMD_ABORT_ON_ERROR). */
 int ksw2amd_sg_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 int ksw2amd_sg_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
 int ksw2amd_sg(void *q, int tlen, const uint8_t *target, int gapo, int gape, int *qe, int *te);
+
+/* Semi-global alignment with the interval's start and a CIGAR (new): what a read mapper needs
+ * after ksw2amd_sg_batch -- target[tb..te] and the path -- as one call instead of a host reversal and two more batch calls.  For every pair:
+ *   score, qe, te   bit for bit what ksw2amd_sg_batch returns; qb = 0 whenever qlen > 0;
+ *   tb              with G(x) the global score of the whole query against target[x..te] under the scalar ksw_extz contract (w = -1,
+ *                   zdrop = -1), and G(te + 1) = -(gapo + qlen * gape), the empty interval with the whole query inserted: the LARGEST x
+ *                   in [0, te + 1] with G(x) == score -- the shortest optimal interval (such an x always exists).  tb == te + 1 says that
+ *                   the interval is empty; it is the answer whenever inserting the whole query is optimal (the empty interval wins its
+ *                   ties), where ksw2amd_sg_batch reports te = 0, so tb = 1.  In the reference's terms: with r = ksw_extz(reverse(query),
+ *                   reverse(target[0..te]), w = -1, zdrop = -1, KSW_EZ_SCORE_ONLY), tb = te - r.mqe_t when r.mqe > -(gapo + qlen * gape),
+ *                   te + 1 otherwise;
+ *   cigar           non-empty interval: exactly the CIGAR of the scalar ksw_extz(km, qlen, query, te-tb+1, target+tb, m, mat, gapo, gape,
+ *                   -1, -1, KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)), &ez), whose score equals `score` (checked for
+ *                   every pair; a mismatch is reported as an error, never returned).  Empty interval: the one operation qlen I
+ *                   (qlen << 4 | 1).
+ * flag: KSW_EZ_SCORE_ONLY (coordinates only, n_cigar = 0, no third stage), KSW_EZ_RIGHT, KSW_EZ_REV_CIGAR; any other bit is
+ * KSW2AMD_E_PARAM.  Nothing is launched for qlen <= 0 -> score 0, qb = qe = tb = te = -1, n_cigar 0; nor for tlen <= 0 with qlen > 0 ->
+ * score -(gapo + qlen * gape), qb 0, qe qlen - 1, te -1, tb 0, and the CIGAR qlen I unless KSW_EZ_SCORE_ONLY.  Arguments, ranges (the
+ * 0x3fffffff limit included) and residue codes as for ksw2amd_sg_batch, all checked before anything is staged or launched; a matrix
+ * without a positive entry is legal; aln == NULL with n > 0 is KSW2AMD_E_PARAM.  The start pass runs on the device from what the forward
+ * pass left there (no download, host reversal or second upload in between).  aln[] is zero-initialised by the caller or holds reusable
+ * CIGAR buffers (cigar / m_cigar, grown through km), as for ksw2amd_ll_align_batch.  The flat entry has the chunking, the on-device code
+ * check, the reset and error semantics and the on_device behaviour of ksw2amd_ll_align_batch_flat (device arena: the spans of the aligned
+ * intervals come back once for the CIGAR stage; on a failure every aln[] entry holds score 0, coordinates -1, n_cigar 0).
+ * ksw2amd_sg_align: one pair on a ksw_ll_qinit profile; returns the score; on a failure 0 with those reset values, reported like
+ * ksw_ll_i16.  Device failures: a negative code, no CPU fallback.
+ * Not computed, here either: the two-piece gap cost, free query ends, a suboptimal score. */
+int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
+                           const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
+                                const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
+int ksw2amd_sg_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

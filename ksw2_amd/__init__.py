@@ -114,7 +114,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
            "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
            "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
-           "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg"]
+           "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
+           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -126,7 +127,8 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_ll_sub_batch", "ksw2amd_ll_sub_batch_flat", "ksw2amd_ll_sub",
                 "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
                 "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
-                "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg"]
+                "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
+           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -285,6 +287,10 @@ class Library:
             L.ksw2amd_sg_batch.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
             L.ksw2amd_sg_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
             L.ksw2amd_sg.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+        if hasattr(L, "ksw2amd_sg_align_batch"):    # (nor the start pass's twin: tests/sga_util.py adds it)
+            L.ksw2amd_sg_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_sg_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_sg_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -757,6 +763,48 @@ class Library:
         finally:
             _libc.free(prof)
         return int(score), qe.value, te.value
+
+    def sg_align_batch(self, queries, targets, mat, gapo, gape, flag=0, m=None, pairs=None, n=None, aln=None):
+        """ksw2amd_sg_align_batch(km=NULL, ...): sg_batch plus the start of the interval and the CIGAR -> list of dicts score, qb (0), qe,
+        tb, te, n_cigar, cigar (the whole query against target[tb..te]; tb == te + 1: the empty interval, CIGAR qlen I; flag:
+        KSW_EZ_SCORE_ONLY / KSW_EZ_RIGHT / KSW_EZ_REV_CIGAR).  aln: a LocalAln array that the caller keeps, as for ll_align_batch_flat."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_sg_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, flag, n, pairs, aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def sg_align_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, flag=0, m=None, device_base=None, aln=None):
+        """ksw2amd_sg_align_batch_flat(km=NULL, ...): sg_align_batch on an arena (see ll_batch_flat) -> list of dicts."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_sg_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, flag, n, ctypes.byref(f), aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def sg_align(self, query, target, mat, gapo, gape, flag=0, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_sg_align(km=NULL, ...) -> dict like sg_align_batch's."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            a = LocalAln()
+            score = self.lib.ksw2amd_sg_align(None, prof, len(ta), tp, gapo, gape, flag, ctypes.byref(a))
+        finally:
+            _libc.free(prof)
+        d = self._aln_to_dict(a)
+        assert d["score"] == int(score)
+        return d
 
     def make_linear_batch(self, queries, targets, mch, mis, e, w=-1, xdrop=-1):
         return LinearBatch(self, queries, targets, mch, mis, e, w, xdrop)

@@ -324,10 +324,11 @@ typedef struct {
 	ll_fwd_fn fwd;
 	int pk_reg;                        /* 1: the packed kernels have a register-profile form (0: packed tasks take the LDS profile; trace line only) */
 } ll_dual_t;
-/* semi-global mode (ksw2_host_sg.c).  launch = k2a_shim_launch_sg, passed in the same way: only ksw2_host_sg.o names
- * it.  With it (never with rev, sb or du) a chunk runs every pair with rows = target on biased values: smax is max(0, largest entry), the
- * packed form is admitted by ll_sg_pk_admit, a pair without a query or without a target gets its corner result instead of being skipped,
- * and a matrix without a positive entry still launches */
+/* semi-global mode (ksw2_host_sg.c).  launch = k2a_shim_launch_sg, passed in the same way: only ksw2_host_sg.o and
+ * ksw2_host_sga.o name it.  With it (never with sb or du) a chunk runs every pair with rows = target on biased values: smax is max(0, largest
+ * entry), the packed form is admitted by ll_sg_pk_admit, a pair without a query or without a target gets its corner result instead of being
+ * skipped, and a matrix without a positive entry still launches.  With a rev as well (ksw2_host_sga.c): rev is
+ * k2a_shim_launch_sg_rev, the anchored start pass, which only ksw2_host_sga.o names */
 typedef struct {
 	ll_fwd_fn launch;
 } ll_fit_t;

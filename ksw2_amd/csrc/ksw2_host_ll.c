@@ -10,7 +10,8 @@
  * ksw2amd_ll_align_batch (ksw2_host_lla.c) runs its start-cell pass from what a chunk staged here: it hands ll_batch_ex the launch as a
  * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
  * The two-piece entries (ksw2_host_lld.c, ksw2_host_llds.c) hand in their forward, start-cell and profile-writing launches and the second
- * gap pair the same way (ll_dual_t), and the semi-global entries (ksw2_host_sg.c) their launch and mode (ll_fit_t).
+ * gap pair the same way (ll_dual_t), and the semi-global entries (ksw2_host_sg.c; with the start pass as the ll_rev_fn: ksw2_host_sga.c)
+ * their launch and mode (ll_fit_t).
  */
 #include "ksw2_host_int.h"
 
@@ -112,12 +113,15 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
 }
 
 /* semi-global mode: the pairs of a chunk that launch nothing and still have a result -- a query without a target */
-static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2amd_lres_t *res)
+static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2amd_lres_t *res, K2aLLBeg *beg)
 {
 	int i;
 	for (i = 0; i < n; ++i) {
 		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
-		if (ql > 0 && tl <= 0) { res[i].score = -(gapo + ql * gape); res[i].qe = ql - 1; res[i].te = -1; }      /* the whole query inserted before the target */
+		if (ql > 0 && tl <= 0) {                                 /* the whole query inserted before the target */
+			res[i].score = -(gapo + ql * gape); res[i].qe = ql - 1; res[i].te = -1;
+			if (beg) { beg[i].score = res[i].score; beg[i].qb = 0; beg[i].tb = 0; }      /* (rev: the empty interval, tb = te + 1) */
+		}
 	}
 }
 
@@ -135,9 +139,11 @@ static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2a
  * boundary holds 16 bytes per column
  * sb and du together: ksw2amd_lld_sub_batch -- par.oe2 / ge2 and the 16-byte boundary come from du, the forward
  * launch is sb->launch (the caller's two-piece one; du->fwd is not called), rows are the target, and ll_pair_bytes sizes both
- * ft (never with rev, sb or du): ksw2amd_sg_batch -- rows = target for every pair, the forward launch is
+ * ft (never with sb or du): ksw2amd_sg_batch -- rows = target for every pair, the forward launch is
  * ft->launch, smax is max(0, largest entry) and may be 0, the packed form is admitted by ll_sg_pk_admit, and a pair without a query or
- * without a target gets its corner result (ll_fit_corners) once the chunk has passed its checks, instead of being skipped */
+ * without a target gets its corner result (ll_fit_corners) once the chunk has passed its checks, instead of being skipped
+ * ft with rev: ksw2amd_sg_align_batch (ksw2_host_sga.c) -- rev is the caller's anchored start pass; beg[i] = its
+ * score, 0, tb (te + 1 for the empty interval), a corner pair's filled in with its result; the trace lines say "sga" */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft)
 {
@@ -145,7 +151,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
 	const ll_fwd_fn fwd = ft ? ft->launch : du ? du->fwd : k2a_shim_launch_ll;
-	const char *tn = ft ? "sg" : du ? "lld" : "ll";      /* the trace lines' prefix */
+	const char *tn = ft ? (rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
@@ -194,7 +200,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] %s-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers", sb->excl,
 	                              du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
-	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, res); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
+	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, res, rev ? beg : 0); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
@@ -308,7 +314,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		for (i = 0; i < ni32; ++i) memcpy(&sub[i32[i].idx], &hs[i32[i].idx], sizeof(K2aLLSub));
 	}
 done:
-	if (ft) ll_fit_corners(src, n, gapo, gape, res);
+	if (ft) ll_fit_corners(src, n, gapo, gape, res, rev ? beg : 0);
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);

@@ -6,8 +6,8 @@
  * Validation, sort, packed pairing, task table, chunks, the flat entry's check and the result scatter are ll_chunk's (ksw2_host_ll.c,
  * ksw2_host_llf.c), told through ll_fit_t what to launch and that the mode is semi-global.
  *
- * This is the only host object that refers to k2a_shim_launch_sg (the simulator builds of the other tests/ *_util.py link the other host
- * objects without one).
+ * Only this host object and ksw2_host_sga.c (ksw2amd_sg_align_batch, which adds the start of the interval and a CIGAR) refer to
+ * k2a_shim_launch_sg (the simulator builds of the other tests/ *_util.py link the other host objects without one).
  */
 #include "ksw2_host_int.h"
 

@@ -1,0 +1,205 @@
+/*
+ * ksw2_host_sga.c -- semi-global alignment with the interval's start and a CIGAR: ksw2amd_sg_align_batch / ksw2amd_sg_align_batch_flat /
+ * ksw2amd_sg_align (include/ksw2_amd.h).  What a caller of ksw2amd_sg_batch does by hand -- reverse the query and
+ * target[0..te] on the host, an extension call for where the whole reversed query ends, another for the CIGAR -- as one call in three stages:
+ *   1. the forward pass of ksw2amd_sg_batch: score, qe = qlen - 1, te;
+ *   2. the anchored start pass, launched behind it on what it left in device memory -- task table, pen tables, sequences, results; no
+ *      download, host reversal or second upload in between (k2a_shim_launch_sg_rev, handed to ll_batch_ex as its ll_rev_fn): the largest tb
+ *      at which the whole query against target[tb..te] scores `score` globally, te + 1 for the empty interval;
+ *   3. the CIGAR of the pairs with a non-empty interval: the scalar-contract ksw_extz, unbanded, on query x target[tb..te] through the batch
+ *      machinery of ksw2amd_extz_batch.  Its score must equal the semi-global score: anything else is reported as an internal error.  An
+ *      empty interval's CIGAR, qlen I, is written here.
+ *
+ * This is the only host object that refers to k2a_shim_launch_sg_rev (it names k2a_shim_launch_sg too, like ksw2_host_sg.c).
+ */
+#include "ksw2_host_int.h"
+
+static void sga_reset(int n, ksw2amd_laln_t *aln)
+{
+	int i;
+	for (i = 0; aln && i < n; ++i) { aln[i].score = 0; aln[i].qb = aln[i].qe = aln[i].tb = aln[i].te = -1; aln[i].n_cigar = 0; }
+}
+
+static inline int sga_has_interval(const ksw2amd_laln_t *a) { return a->qe >= 0 && a->te >= 0 && a->tb <= a->te; }
+
+/* after stages 1 and 2: aln[i] = score, the query's ends and the interval, the start pass checked against the forward pass (no CIGAR
+ * yet).  qlen / tlen: the pairs' lengths, `stride` ints apart.  Returns through *na the pairs with a non-empty interval */
+static int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na_)
+{
+	int i, na = 0;
+	char msg[96];
+	for (i = 0; i < n; ++i) {
+		ksw2amd_laln_t *a = &aln[i];
+		const int ql = qlen[i * stride], tl = tlen[i * stride];
+		a->score = res[i].score; a->qe = res[i].qe; a->te = res[i].te; a->qb = beg[i].qb; a->tb = beg[i].tb;
+		a->n_cigar = 0;
+		if (ql <= 0) { a->score = 0; a->qb = a->qe = a->tb = a->te = -1; continue; }
+		if (tl <= 0) { a->qb = 0; a->tb = 0; continue; }               /* the whole query inserted before the target: te = -1, empty interval */
+		/* the best global score of the query against an interval that ends in te is the forward score itself */
+		if (beg[i].score != res[i].score || beg[i].qb != 0 || beg[i].tb < 0 || beg[i].tb > res[i].te + 1) {
+			snprintf(msg, sizeof(msg), "%d: forward %d, reversed %d (tb %d, te %d)", i, res[i].score, beg[i].score, beg[i].tb, res[i].te);
+			return fail(KSW2AMD_E_NODEVICE, "semi-global alignment: internal error, start pass disagrees with the forward pass on pair %s", msg);
+		}
+		na += sga_has_interval(a);
+	}
+	*na_ = na;
+	return KSW2AMD_OK;
+}
+
+/* stage 3.  Empty intervals: qlen I, written here.  The na pairs with an interval: query x target[tb..te] as extension pairs into HOST
+ * memory; the caller's CIGAR buffers travel through ez[] and back.  at_start = 0: pairs[i].target is the full target; 1: it already points
+ * at residue tb (the intervals of a device arena, brought back).  pairs[i].query is the whole query either way */
+static int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln)
+{
+	ksw2amd_pair_t *pp = 0;
+	ksw_extz_t *ez = 0;
+	int32_t *idx = 0;
+	int i, k, rc = KSW2AMD_OK;
+	char msg[96];
+	for (i = 0; i < n; ++i) {
+		ksw2amd_laln_t *a = &aln[i];
+		ksw_extz_t z;
+		if (a->qe < 0 || sga_has_interval(a)) continue;
+		z.cigar = a->cigar; z.m_cigar = a->m_cigar;
+		ez_reserve(km, &z, 1);
+		a->cigar = z.cigar; a->m_cigar = z.m_cigar;
+		if (!a->cigar) { a->m_cigar = 0; return fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); }
+		a->cigar[0] = (uint32_t)(a->qe + 1) << 4 | 1u;
+		a->n_cigar = 1;
+	}
+	if (na == 0) return KSW2AMD_OK;
+	pp = (ksw2amd_pair_t*)malloc(sizeof(*pp) * (size_t)na);
+	ez = (ksw_extz_t*)calloc((size_t)na, sizeof(*ez));
+	idx = (int32_t*)malloc(sizeof(*idx) * (size_t)na);
+	if (!pp || !ez || !idx) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
+	for (i = 0, k = 0; i < n; ++i) {
+		const ksw2amd_laln_t *a = &aln[i];
+		if (!sga_has_interval(a)) continue;
+		pp[k].query = pairs[i].query; pp[k].qlen = a->qe + 1;
+		pp[k].target = pairs[i].target + (at_start ? 0 : a->tb); pp[k].tlen = a->te - a->tb + 1;
+		pp[k].w = -1; pp[k].zdrop = -1; pp[k].end_bonus = 0;
+		pp[k].flag = KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR));
+		ez[k].cigar = a->cigar; ez[k].m_cigar = a->m_cigar;
+		idx[k++] = i;
+	}
+	{
+		ksw2amd_scoring_t sc;
+		sc.m = m; sc.mat = mat; sc.q = (int8_t)gapo; sc.e = (int8_t)gape; sc.q2 = 0; sc.e2 = 0;
+		rc = ext_batch_scalar(0, km, &sc, na, pp, ez);
+	}
+	for (k = 0; k < na; ++k) {                 /* the buffers may have grown or moved: always hand them back */
+		ksw2amd_laln_t *a = &aln[idx[k]];
+		a->cigar = ez[k].cigar; a->m_cigar = ez[k].m_cigar;
+		a->n_cigar = rc == KSW2AMD_OK ? ez[k].n_cigar : 0;
+	}
+	for (k = 0; k < na && rc == KSW2AMD_OK; ++k)
+		if (ez[k].score != aln[idx[k]].score) {
+			snprintf(msg, sizeof(msg), "%d: semi-global %d, global %d", (int)idx[k], aln[idx[k]].score, ez[k].score);
+			rc = fail(KSW2AMD_E_NODEVICE, "semi-global alignment: internal error, the interval's global score differs from the semi-global score on pair %s", msg);
+		}
+out:
+	free(pp); free(ez); free(idx);
+	return rc;
+}
+
+static int sga_check_flag(int flag)
+{
+	if (flag & ~LLA_FLAGS) return fail(KSW2AMD_E_PARAM, "semi-global alignment: flag accepts KSW_EZ_SCORE_ONLY, KSW_EZ_RIGHT and KSW_EZ_REV_CIGAR only%s", "");
+	return KSW2AMD_OK;
+}
+
+int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+{
+	ksw2amd_lres_t *res = 0;
+	K2aLLBeg *beg = 0;
+	ll_fit_t ft;
+	int na = 0, rc;
+	/* every argument before anything is staged: the flag here, m / mat / gap costs / pair array / ranges / residue codes in ll_batch_ex */
+	if ((rc = sga_check_flag(flag)) != KSW2AMD_OK) return rc;
+	if (n > 0 && !aln) return fail(KSW2AMD_E_PARAM, "semi-global alignment: bad pair array%s", "");
+	if (n > 0) {
+		res = (ksw2amd_lres_t*)malloc(sizeof(*res) * (size_t)n);
+		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
+		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
+	}
+	ft.launch = k2a_shim_launch_sg;
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_sg_rev, beg, 0, 0, 0, &ft)) != KSW2AMD_OK) goto out;
+	if (n == 0) goto out;
+	if ((rc = sga_cells(n, &pairs[0].qlen, &pairs[0].tlen, sizeof(pairs[0]) / sizeof(int32_t), res, beg, aln, &na)) != KSW2AMD_OK) goto out;
+	if (flag & KSW_EZ_SCORE_ONLY) goto out;
+	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln);
+out:
+	if (rc != KSW2AMD_OK) sga_reset(n, aln);
+	free(res); free(beg);
+	return rc;
+}
+
+int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
+{
+	ksw2amd_lres_t *res = 0;
+	K2aLLBeg *beg = 0;
+	ksw2amd_lpair_t *pp = 0;
+	uint8_t *host = 0;
+	ll_fit_t ft;
+	int i, na = 0, rc;
+	if ((rc = sga_check_flag(flag)) != KSW2AMD_OK) return rc;
+	if (n > 0 && !aln) return fail(KSW2AMD_E_PARAM, "semi-global alignment: bad flat batch arguments%s", "");
+	if (n > 0) {
+		res = (ksw2amd_lres_t*)malloc(sizeof(*res) * (size_t)n);
+		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
+		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
+	}
+	/* stages 1 and 2 on the borrowed arena */
+	ft.launch = k2a_shim_launch_sg;
+	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, k2a_shim_launch_sg_rev, beg, 0, 0, 0, &ft)) != KSW2AMD_OK) goto out;
+	if (n == 0) goto out;
+	if ((rc = sga_cells(n, in->qlen, in->tlen, 1, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
+	if (flag & KSW_EZ_SCORE_ONLY) goto out;
+	/* stage 3: the whole query x [toff + tb, toff + te] under the scalar ksw_extz contract.  Host arena: pointers into it.  Device arena: the
+	 * span of the aligned intervals and their queries comes back in one copy, then the same pointer path */
+	pp = (ksw2amd_lpair_t*)malloc(sizeof(*pp) * (size_t)n);
+	if (!pp) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
+	if (in->on_device && na > 0) {
+		uint64_t lo = UINT64_MAX, hi = 0;
+		void *st = thread_stream();
+		for (i = 0; i < n; ++i) {
+			const ksw2amd_laln_t *a = &aln[i];
+			if (!sga_has_interval(a)) continue;
+			if (in->qoff[i] < lo) lo = in->qoff[i];
+			if (in->toff[i] + (uint64_t)a->tb < lo) lo = in->toff[i] + (uint64_t)a->tb;
+			if (in->qoff[i] + (uint64_t)a->qe + 1 > hi) hi = in->qoff[i] + (uint64_t)a->qe + 1;
+			if (in->toff[i] + (uint64_t)a->te + 1 > hi) hi = in->toff[i] + (uint64_t)a->te + 1;
+		}
+		host = (uint8_t*)malloc((size_t)(hi - lo));
+		if (!host) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
+		if (!st || k2a_shim_d2h(host, in->base + lo, (size_t)(hi - lo), st) || k2a_shim_stream_sync(st)) { rc = fail(KSW2AMD_E_NODEVICE, "semi-global alignment: %s", k2a_shim_last_error()); goto out; }
+		for (i = 0; i < n; ++i) {
+			const ksw2amd_laln_t *a = &aln[i];
+			pp[i].query = pp[i].target = 0; pp[i].qlen = in->qlen[i]; pp[i].tlen = in->tlen[i];
+			if (!sga_has_interval(a)) continue;
+			pp[i].query = host + (in->qoff[i] - lo); pp[i].target = host + (in->toff[i] + (uint64_t)a->tb - lo);
+		}
+	} else
+		for (i = 0; i < n; ++i) {                 /* (a device arena without an interval: the pointers are never followed) */
+			pp[i].query = in->base + in->qoff[i]; pp[i].target = in->base + in->toff[i]; pp[i].qlen = in->qlen[i]; pp[i].tlen = in->tlen[i];
+		}
+	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pp, in->on_device != 0, na, aln);
+out:
+	if (rc != KSW2AMD_OK) sga_reset(n, aln);
+	free(res); free(beg); free(pp); free(host);
+	return rc;
+}
+
+/* one pair on a ksw_ll_qinit profile: entry 0 of ksw2amd_sg_align_batch, failures reported like ksw_ll_i16 */
+int ksw2amd_sg_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln)
+{
+	const ll_prof_t *p = (const ll_prof_t*)q;
+	ksw2amd_lpair_t pr;
+	int rc;
+	sga_reset(aln ? 1 : 0, aln);
+	if (!p || !aln) { rc = fail(KSW2AMD_E_PARAM, "ksw2amd_sg_align: NULL profile or result%s", ""); call_failed("ksw2amd_sg_align", rc, 0); return 0; }
+	pr.query = (const uint8_t*)(p + 1); pr.qlen = p->qlen; pr.target = target; pr.tlen = tlen;
+	rc = ksw2amd_sg_align_batch(km, p->m, (const int8_t*)(p + 1) + imax(p->qlen, 0), gapo, gape, flag, 1, &pr, aln);
+	if (rc != KSW2AMD_OK) { call_failed("ksw2amd_sg_align", rc, 0); return 0; }
+	return aln->score;
+}

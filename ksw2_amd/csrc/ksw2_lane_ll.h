@@ -101,13 +101,18 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * length l: a second pair of gap states E2 / F2 under (oe2, ge2) beside E / F, clamped at 0 like them (max(0, .., max(X, 0)) = max(0, .., X),
  * and max(H - oe, max(X, 0) - ge, 0) = max(max(H - oe, X - ge), 0) because -ge <= 0: H never sees the clamp), f2[] per row and
  * an e2 chain down the strip that reaches the lane below (and the boundary) with H and E.  With DUAL = false nothing of it exists. */
-/* FIT (rows = target, never with REV / SUB / DUAL): the semi-global mode of ksw2amd_sg_batch -- the whole query
+/* FIT (rows = target, never with SUB / DUAL): the semi-global mode of ksw2amd_sg_batch -- the whole query
  * against the best interval of the target, no clamp at 0.  With B = gapo + ncols * gape every true H(t, j) >= -(gapo + (j + 1) * gape) >= -B
  * (insert the query up to column j), so the cell update runs unchanged on H' = H + B >= 0; E' and F' held clamped at 0 stand for values
  * <= -B, which reach an H only where H = -B itself.  What differs is the boundary -- column -1 is B in every row (H(t, -1) = 0), row -1 is
  * B - (gapo + (j + 1) * gape) = (ncols - 1 - j) * gape (fit_top) -- and the maximum: it is taken over the last column only, which is what
  * hl[] holds when a lane has walked its columns, so step() keeps no row maximum at all and gen_end folds hl[] into (largest H', smallest
- * row).  The key starts at -1, below any H'; the score is H' - B. */
+ * row).  The key starts at -1, below any H'; the score is H' - B.
+ * FIT with REV: the start pass of ksw2amd_sg_align_batch -- the global alignment of the whole reversed query against
+ * the reversed target prefix that ends in the forward pass's row te, anchored at (te, ncols - 1) and free to end in any row.  Row i holds
+ * r[te - i] (rl = te + 1), column j holds c[ncols - 1 - j] (cl = ncols for every half).  Row -1 is fit_top as it stands; column -1 is the
+ * global boundary H'(i, -1) = B - (gapo + (i + 1) * gape) = (ncols - 1 - i) * gape held at 0 (fit_left) where the forward pass has B.  The key
+ * starts at (0, row -1): H'(-1, ncols - 1) = 0 is the empty interval, and k2a_ll_better lets it win its ties. */
 template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
@@ -142,7 +147,7 @@ struct K2aLaneLL {
 		for (int h = 0; h < NH; ++h) k2a_ll_key_reset(key[h]);
 		if (FIT) {
 			bias = (uint32_t)(par.oe - par.ge + ncols * par.ge) * x;
-			for (int h = 0; h < NH; ++h) key[h].s = -1;
+			if (!REV) for (int h = 0; h < NH; ++h) key[h].s = -1;      /* REV: (0, -1), row -1 of the last column */
 		}
 	}
 
@@ -154,11 +159,17 @@ struct K2aLaneLL {
 		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u);
 	}
 
+	/* FIT with REV: column -1 of row i, H'(i, -1) = max(ncols - 1 - i, 0) * gape (i = -1: B) */
+	K2A_FN uint32_t fit_left(int i) const
+	{
+		return i < 0 ? bias : (uint32_t)(k2a_max(ncols - 1 - i, 0) * (int)(ge & (PK ? 0xffffu : 0xffffffffu))) * (PK ? 0x10001u : 1u);
+	}
+
 	/* start generation g: this lane's rows, their profile, zeroed columns (tab = the task's pen table in LDS, [row code * m + column code]) */
 	K2A_FN void gen_begin(int g, const uint8_t *r0, const uint8_t *r1, const uint8_t *tab)
 	{
 		i0 = g * K2A_LL_ROWS + lane * C;
-		hu_prev = FIT ? bias : 0u;
+		hu_prev = !FIT ? 0u : REV ? fit_left(i0 - 1) : bias;
 		const uint32_t f0 = !FIT ? 0u : PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);      /* FIT: F'(i, 0) = sat(B - oe) */
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
@@ -170,7 +181,8 @@ struct K2aLaneLL {
 			} else {
 				a = i < nrows ? r0[i] : 0u; b = (PK && i < nrows) ? r1[i] : 0u;
 			}
-			hl[c] = FIT ? bias : 0u; f[c] = f0; rmax[c] = 0; rcol[c] = 0;
+			hl[c] = !FIT ? 0u : REV ? fit_left(i) : bias; rmax[c] = 0; rcol[c] = 0;
+			f[c] = !(FIT && REV) ? f0 : PK ? k2a_ll_subs(hl[c], oe) : (uint32_t)k2a_max((int)hl[c] - (int)oe, 0);      /* F'(i, 0) = sat(H'(i, -1) - oe) */
 			if (DUAL) f2[DUAL ? c : 0] = 0;
 			if (LDSP) {
 				pa[c] = a * (uint32_t)m;

@@ -208,9 +208,16 @@ int k2a_shim_launch_lld_sub(int pk, int lds, const K2aLL *par, const K2aLLTask *
 /* ksw2amd_sg_batch: the semi-global mode on the task table of k2a_shim_launch_ll with rows = target
  * (tasks[].swapped = 0) and par->smax = max(0, largest entry): H' = H + gapo + ncols * gape through the same cell update, the free
  * start in the target and the inserted query prefix as boundary values, the maximum over the last column.  res[slot] = (score, ncols - 1,
- * te), the smallest te on a tie.  Only ksw2_host_sg.c calls it (the other simulator builds have no such symbol). */
+ * te), the smallest te on a tie.  Only ksw2_host_sg.c and ksw2_host_sga.c call it (the other simulator builds have no such symbol). */
 int k2a_shim_launch_sg(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                        uint8_t *scratch, K2aLLRes *res, void *stream);
+/* Start pass of ksw2amd_sg_align_batch, on the SAME task table, tables, sequences and scratch, behind
+ * k2a_shim_launch_sg in `stream`: half h of a task reads te from res[tasks[t].res[h]] in device memory and aligns the whole reversed query
+ * globally against reverse(rows[0 .. te]), anchored at (te, ncols - 1) and free to end in any row.  beg[slot] = (that pass's score, 0, tb):
+ * the largest tb at which the score is reached, te + 1 for the empty interval.  Only ksw2_host_sga.c calls it (the other simulator builds
+ * have no such symbol). */
+int k2a_shim_launch_sg_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
 
 #ifdef __cplusplus
 }

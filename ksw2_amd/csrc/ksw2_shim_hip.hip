@@ -2222,7 +2222,10 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * per step, and a boundary entry of 16 bytes per column (H, E, E2, pad) stored and prefetched as one access.
  * SUB (k2a_ll_fsub_kernel; with DUAL: k2a_lld_fsub_kernel): the forward pass that also streams every generation's row maxima to `prof`.
  * FIT (k2a_sg_kernel): the semi-global mode on biased values.  Rows are the target; lane 0 of the first generation
- * takes row -1 from K2aLaneLL::fit_top instead of zeros, and the score leaves the bias behind. */
+ * takes row -1 from K2aLaneLL::fit_top instead of zeros, and the score leaves the bias behind.
+ * FIT with REV (k2a_sg_rev_kernel): the start pass of ksw2amd_sg_align_batch.  Half h runs rows target[te_h - i] and
+ * the whole reversed query, whatever the sign of its score; beg[tk.res[h]] = score of the pass, 0, te_h - (best row), the best row being -1
+ * for the empty interval. */
 template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
@@ -2250,10 +2253,11 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 #pragma unroll
 		for (int h = 0; h < (PK ? 2 : 1); ++h) {
 			const K2aLLRes r = fres[tk.res[h]];
-			const bool pos = r.score > 0;
+			const bool pos = FIT || r.score > 0;       /* FIT: a score may be <= 0, and every launched pair has its row te >= 0 */
 			fq[h] = r.qe; ft[h] = r.te;
 			rl[h] = pos ? (tk.swapped ? r.qe : r.te) + 1 : 0;
-			cl[h] = pos ? (tk.swapped ? r.te : r.qe) + 1 : 0;
+			cl[h] = FIT ? tk.ncols : pos ? (tk.swapped ? r.te : r.qe) + 1 : 0;      /* FIT: the whole query */
+			if (FIT) rl[h] = k2a_max(rl[h], 0);
 			rl[h] = k2a_min(rl[h], tk.nrows); cl[h] = k2a_min(cl[h], tk.ncols);      /* a forward cell always lies inside; never trust it for an address */
 		}
 		L.set_limits(rl, cl);
@@ -2322,7 +2326,10 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 			k.s = take ? s : k.s; k.te = take ? te : k.te; k.qe = take ? qe : k.qe;
 		}
 		if (lane == 0 && (h == 0 || tk.res[1] != tk.res[0])) {
-			if (REV) {
+			if (REV && FIT) {                          /* k.te = -1: the empty interval, tb = te + 1 */
+				K2aLLBeg b; b.score = k.s - L.fit_bias(); b.qb = 0; b.tb = ft[h] - k.te;
+				beg[tk.res[h]] = b;
+			} else if (REV) {
 				const bool pos = k.s > 0;
 				K2aLLBeg b; b.score = k.s; b.qb = pos ? fq[h] - k.qe : -1; b.tb = pos ? ft[h] - k.te : -1;
 				beg[tk.res[h]] = b;
@@ -2357,6 +2364,15 @@ k2a_sg_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, 
               uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
 {
 	k2a_ll_task<PK, LDSP, false, false, false, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+/* ... and where that interval starts (ksw2amd_sg_align_batch): the anchored reverse pass behind k2a_sg_kernel */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_sg_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                  uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true, false, false, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
 /* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
@@ -2917,6 +2933,22 @@ int k2a_shim_launch_sg(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
 	else if (pk) hipLaunchKernelGGL((k2a_sg_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else if (lds) hipLaunchKernelGGL((k2a_sg_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else hipLaunchKernelGGL((k2a_sg_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* start pass of ksw2amd_sg_align_batch: the same grid over the same task table, behind k2a_shim_launch_sg in the stream */
+int k2a_shim_launch_sg_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "semi-global alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_sg_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (pk) hipLaunchKernelGGL((k2a_sg_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (lds) hipLaunchKernelGGL((k2a_sg_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_sg_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -55,7 +55,14 @@ k2a_ll_sub_kernel, the ratio (k2a_lld_fsub_kernel + k2a_ll_sub_kernel) / k2a_lld
 that its target is the longer sequence (both entries then run it with rows = target), the library call alone in the clock on both sides
 and the two entries ALTERNATING batch by batch in one process; pairs/s and GCUPS (qlen x tlen cells) of both, their ratio, the spread of
 the ll_batch batches, the forms both took and a parity sample against tests/sg_oracle.c.  --ktrace: per batch the time of k2a_ll_kernel
-and of k2a_sg_kernel, their ratio and the batch-to-batch spread of k2a_ll_kernel."""
+and of k2a_sg_kernel, their ratio and the batch-to-batch spread of k2a_ll_kernel.
+
+  python tools/scripts/ll_bench.py --workload A --sg-align [--ktrace kernel_trace.csv] [--out profiles/sga_bench_A.json]
+
+--sg-align: ksw2amd_sg_align_batch on the pair array of --sg: ksw2amd_sg_batch, ksw2amd_sg_align_batch with
+KSW_EZ_SCORE_ONLY, ksw2amd_sg_align_batch with CIGARs, and the by-hand pattern they replace (sg_batch, host reversal, ksw2amd_extz_batch for
+mqe_t, ksw2amd_extz_batch for the CIGAR) alternate batch by batch, a warm-up plus --reps batches each, library calls only in the clock (the
+by-hand pattern's host work is reported beside it).  --ktrace: per batch the time of k2a_sg_kernel and of k2a_sg_rev_kernel."""
 import argparse
 import ctypes
 import csv
@@ -364,6 +371,120 @@ def main_sg(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["parity_ok"] else 1
 
 
+def main_sg_align(a, lib, q, t, mat, gapo, gape, cells, form):
+    """--sg-align: ksw2amd_sg_batch, ksw2amd_sg_align_batch (SCORE_ONLY, and with CIGARs) and the by-hand pattern they replace, alternating"""
+    from tests import sga_util as sga
+    swap = [len(x) > len(y) for x, y in zip(q, t)]
+    q, t = [y if w else x for x, y, w in zip(q, t, swap)], [x if w else y for x, y, w in zip(q, t, swap)]      # target >= query, as --sg
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res = np.zeros((n, 3), dtype=np.int32)
+    alns = dict(sga_coords=(ksw2_amd.LocalAln * n)(), sga_cigar=(ksw2_amd.LocalAln * n)())      # CIGAR buffers are reused from batch to batch
+    rp = lambda x, ty: x.ctypes.data_as(ctypes.POINTER(ty))
+    hand = {}
+
+    def sg_batch():
+        return L.ksw2amd_sg_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(res, ksw2_amd.LocalResult))
+
+    def by_hand():
+        """sg_batch, host reversal, ksw2amd_extz_batch for mqe_t, ksw2amd_extz_batch for the CIGAR; the time inside the three library calls
+        and the host work between them are kept apart"""
+        c = dict(lib=0.0, host=0.0)
+        r = np.zeros((n, 3), dtype=np.int32)
+        t0 = time.perf_counter()
+        rc = L.ksw2amd_sg_batch(5, mp.ctypes.data_as(i8p), gapo, gape, n, pairs, rp(r, ksw2_amd.LocalResult))
+        t1 = time.perf_counter()
+        b1 = lib.make_batch([np.ascontiguousarray(x[::-1]) for x in q], [np.ascontiguousarray(y[te::-1]) for y, te in zip(t, r[:, 2])],
+                            mat, gapo, gape, w=-1, zdrop=-1, flag=SCORE_ONLY)
+        ez1 = (ksw2_amd.KswExtz * n)()
+        t2 = time.perf_counter()
+        rc |= L.ksw2amd_extz_batch(None, ctypes.byref(b1.sc), n, b1.pairs, ez1)
+        t3 = time.perf_counter()
+        tb = [int(te) - ez1[i].mqe_t if ez1[i].mqe > -(gapo + len(q[i]) * gape) else int(te) + 1 for i, te in enumerate(r[:, 2])]
+        live = [i for i in range(n) if tb[i] <= r[i, 2]]
+        b2 = lib.make_batch([q[i] for i in live], [t[i][tb[i]:r[i, 2] + 1] for i in live], mat, gapo, gape, w=-1, zdrop=-1, flag=GENERIC_SC)
+        ez2 = (ksw2_amd.KswExtz * max(len(live), 1))()
+        t4 = time.perf_counter()
+        rc |= L.ksw2amd_extz_batch(None, ctypes.byref(b2.sc), len(live), b2.pairs, ez2)
+        t5 = time.perf_counter()
+        c["lib"], c["host"] = (t1 - t0) + (t3 - t2) + (t5 - t4), (t2 - t1) + (t4 - t3)
+        hand.update(tb=tb, live=live, cigar={i: [int(ez2[k].cigar[j]) for j in range(ez2[k].n_cigar)] for k, i in enumerate(live) if k % 97 == 0},
+                    lib_s=hand.get("lib_s", []) + [c["lib"]], host_s=hand.get("host_s", []) + [c["host"]])
+        for k in range(len(live)):
+            ksw2_amd._libc.free(ctypes.cast(ez2[k].cigar, ctypes.c_void_p))
+        return rc
+
+    fns = dict(sg_batch=sg_batch,
+               sga_coords=lambda: L.ksw2amd_sg_align_batch(None, 5, mp.ctypes.data_as(i8p), gapo, gape, SCORE_ONLY, n, pairs, alns["sga_coords"]),
+               sga_cigar=lambda: L.ksw2amd_sg_align_batch(None, 5, mp.ctypes.data_as(i8p), gapo, gape, 0, n, pairs, alns["sga_cigar"]),
+               by_hand=by_hand)
+    tags = dict(sg_batch="sg: pairs", sga_coords="sga", sga_cigar="sga", by_hand="sg: pairs")
+    forms = {}
+    os.environ["KSW2AMD_TRACE"] = "1"                          # the warm-ups' form lines
+    for name, fn in fns.items():
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            forms[name] = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tags[name] in l]
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+    os.environ.pop("KSW2AMD_TRACE")
+    hand["lib_s"], hand["host_s"] = [], []                     # (the warm-up's)
+    times = {k: [] for k in fns}
+    for _ in range(a.reps):                                    # alternating: sg, coords, cigar, by hand, sg, ...
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    times["by_hand"] = hand["lib_s"]                           # the three library calls only, like the others
+    rec = dict(workload=a.workload, mode="sg-align", pairs=n, cells=cells, ll_form=form, pairs_turned_round=int(sum(swap)),
+               clock="library calls only: pair and result arrays are built before them; the four alternate batch by batch; by_hand = the sum of "
+                     "its three library calls, the host reversal and the pair arrays between them in by_hand_host_s")
+    for name in fns:
+        ts = times[name]
+        rec[name] = dict(e2e_s=min(ts), e2e_all_s=ts, pairs_per_s=n / min(ts), e2e_gcups=cells / min(ts) / 1e9, forms=forms[name][:4])
+    rec["by_hand_host_s"] = hand["host_s"]
+    rec["sg_e2e_spread"] = (max(times["sg_batch"]) - min(times["sg_batch"])) / min(times["sg_batch"])
+    al = alns["sga_cigar"]
+    rec["empty_intervals"] = int(sum(al[i].tb > al[i].te for i in range(n)))
+    rec["mean_interval"] = float(np.mean([al[i].te - al[i].tb + 1 for i in range(n)]))
+    rec["by_hand_agrees"] = bool(all(hand["tb"][i] == al[i].tb and res[i, 2] == al[i].te and res[i, 0] == al[i].score for i in range(n))
+                                 and all([int(al[i].cigar[j]) for j in range(al[i].n_cigar)] == c for i, c in hand["cigar"].items()))
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = sga.oracle_cells([q[i] for i in idx], [t[i] for i in idx], mat, gapo, gape, 5)
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool(all(tuple(exp[k]) == (al[i].score, al[i].qb, al[i].qe, al[i].tb, al[i].te) for k, i in enumerate(idx))
+                            and all(tuple(exp[k]) == tuple(getattr(alns["sga_coords"][i], f) for f in ("score", "qb", "qe", "tb", "te")) for k, i in enumerate(idx)))
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        per = nl(forms["sg_batch"][0])
+        kf = trace_batches(a.ktrace, "k2a_sg_kernel", per)     # in dispatch order: warm-ups sg, coords, cigar, by hand, then reps x the same four
+        kr = trace_batches(a.ktrace, "k2a_sg_rev_kernel", per)
+        fwd_sg = [kf[4 + 4 * r] for r in range(a.reps) if 4 + 4 * r < len(kf)]                 # the forward kernel of the sg_batch batches
+        fwd_all = kf[4:]
+        rev = kr[2:]                                                                         # coords, cigar alternating
+        rec["kernel"] = dict(sg_kernel_ms_of_sg_batch=fwd_sg, sg_kernel_ms_all=fwd_all, sg_rev_kernel_ms=rev,
+                             sg_kernel_spread=(max(fwd_all) - min(fwd_all)) / min(fwd_all) if fwd_all else None,
+                             rev_over_fwd=(sum(rev) / len(rev)) / (sum(fwd_all) / len(fwd_all)) if rev and fwd_all else None)
+    for x in alns["sga_cigar"]:
+        ksw2_amd._libc.free(ctypes.cast(x.cigar, ctypes.c_void_p))
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] and rec["by_hand_agrees"] else 1
+
+
 def main_dual(a, lib, q, t, mat, gapo, gape, cells, form):
     from tests import lld_util as ld
     n = len(q)
@@ -534,6 +655,7 @@ def main():
     ap.add_argument("--sub", action="store_true", help="ksw2amd_ll_sub_batch beside ksw2amd_ll_batch on the same pair array, library calls only in the clock")
     ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries; with --sub ksw2amd_lld_sub_batch beside ksw2amd_lld_batch")
     ap.add_argument("--sg", action="store_true", help="ksw2amd_sg_batch beside ksw2amd_ll_batch on the same pair array (target >= query), alternating, library calls only in the clock")
+    ap.add_argument("--sg-align", action="store_true", help="ksw2amd_sg_batch, ksw2amd_sg_align_batch (SCORE_ONLY and with CIGARs) and the by-hand pattern (sg_batch, host reversal, two ksw2amd_extz_batch calls) on the same pair array, alternating")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -550,6 +672,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.sg_align:
+        return main_sg_align(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sg:
         return main_sg(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.dual and a.sub:
