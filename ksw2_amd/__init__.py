@@ -1063,7 +1063,7 @@ class Plan:
 
     def describe(self):
         """ksw2amd_plan_describe -> one dict per kernel class the next run() launches (kernel, G, C, gaps, mode, rebased, nomax,
-        generic, form, tasks)."""
+        generic, form, tasks, uniform, wire4, tn, base = what a packed class's profile bytes are short of: K2aScoring.pk_base)."""
         buf = ctypes.create_string_buffer(16384)
         self.L.lib.ksw2amd_plan_describe(self.h, buf, len(buf))
         out = []

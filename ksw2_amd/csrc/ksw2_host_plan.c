@@ -416,7 +416,7 @@ static void build_scoring(int dual, int m, const int8_t *mat, int q, int e, int 
  * as its penalty below the matrix's largest entry and look it up in per-query-code column profiles (K2aScoring.cp).  A profile
  * has four bytes, target codes 0..3: pairs whose TARGET holds code 4 leave this class (plan_create_ex), a query's code 4 is table
  * entry 4.  What must hold ... */
-typedef struct { int ok, smax, smin, qemax, qemin, q, e, tn1; uint32_t cp[8]; } pkinfo_t;
+typedef struct { int ok, smax, smin, qemax, qemin, q, e, tn1, base, tnc; uint32_t cp[8]; } pkinfo_t;
 
 static void pk_scoring(int dual, int m, const int8_t *mat, int q, int e, int q2, int e2, int generic, pkinfo_t *o)
 {
@@ -427,14 +427,27 @@ static void pk_scoring(int dual, int m, const int8_t *mat, int q, int e, int q2,
 		build_eff(dual, m, mat, e, e2, generic, eff);
 		o->smax = o->smin = eff[0];
 		for (x = 0; x < m * m; ++x) { o->smax = imax(o->smax, eff[x]); o->smin = imin(o->smin, eff[x]); }
+#if K2A_HL_OPEN
+		{	/* column profile of query code y: q + e + s against target codes 0..3 (the rows hold H - q: ksw2_lane_pk.h, "Open form"),
+			 * less the constant that brings every byte into 0..255 -- 0 for every scoring with s >= -(q + e) and q + e + smax <= 255;
+			 * the kernels' TN build adds it back (K2aScoring.pk_base).  smax - smin <= 255: the bytes always fit */
+			int lo = 0x7fffffff, hi = -0x7fffffff;
+			for (y = 0; y < m; ++y)
+				for (x = 0; x < 4 && x < m; ++x) { lo = imin(lo, q + e + eff[x * m + y]); hi = imax(hi, q + e + eff[x * m + y]); }
+			o->base = lo < 0 ? lo : hi > 255 ? hi - 255 : 0;
+			for (y = 0; y < m; ++y)
+				for (x = 0; x < 4 && x < m; ++x) o->cp[y] |= (uint32_t)(q + e + eff[x * m + y] - o->base) << (8 * x);
+		}
+#else
 		for (y = 0; y < m; ++y)                              /* column profile of query code y: penalties against target codes 0..3 */
 			for (x = 0; x < 4 && x < m; ++x) o->cp[y] |= (uint32_t)(o->smax - eff[x * m + y]) << (8 * x);
+#endif
 		/* a TARGET wildcard (code 4) that scores the same against every query code -- every match / mismatch / N matrix -- stays
 		 * in the packed kernels as a row with penalty 0 out of the profile and a constant taken off its candidate
 		 * (K2aScoring.pk_tn1, K2aLanePk::step); KSW2AMD_TN=0: as before round 6 (such pairs take the int32 kernels or are re-run) */
 		if (m == 5 && !(ENV(TN) && ENV(TN)[0] == '0')) {
 			for (y = 1; y < 5 && eff[4 * 5 + y] == eff[4 * 5]; ++y) {}
-			if (y == 5) o->tn1 = o->smax - eff[4 * 5] + 1;
+			if (y == 5) { o->tn1 = o->smax - eff[4 * 5] + 1; o->tnc = q + e + eff[4 * 5] - o->base; }      /* tn1: on / off (and the constant of the form before); tnc: what such a row adds (k2a_tn_fix) */
 		}
 	}
 	o->q = q; o->e = e;
@@ -1059,7 +1072,7 @@ ksw2amd_plan_t *plan_create_ex(int dual, int scalar, const ksw2amd_scoring_t *sc
 			c->cfg = c->solo ? 0 : pass ? (pass - 1) % K2A_NPKCFG : ci / 6; c->rb = pass && !c->solo ? ((pass - 1) / K2A_NPKCFG) & 1 : 0;
 			c->nomax = !c->solo && pass > 2 * K2A_NPKCFG; c->mode = (ci / 2) % 3; c->generic = ci & 1; c->pk = pass != 0 && !c->solo; c->first = k;
 			build_scoring(dual, m, sc->mat, q, e, q2, e2, c->generic, &c->sc);
-			if (pkinfo[c->generic].ok > 0) { memcpy(c->sc.cp, pkinfo[c->generic].cp, sizeof(c->sc.cp)); c->sc.pk_smax = pkinfo[c->generic].smax; c->sc.pk_tn1 = pkinfo[c->generic].tn1; }
+			if (pkinfo[c->generic].ok > 0) { memcpy(c->sc.cp, pkinfo[c->generic].cp, sizeof(c->sc.cp)); c->sc.pk_smax = pkinfo[c->generic].smax; c->sc.pk_tn1 = pkinfo[c->generic].tn1; c->sc.pk_base = pkinfo[c->generic].base; c->sc.pk_tnc = pkinfo[c->generic].tnc; }
 			if (uni) {
 				if (!pass || c->solo) { for (i = 0; i < cnt; ++i) p->h_order[k++] = (uint32_t)i; ntask = cnt; }
 				else for (i = 0; i < cnt; i += 2, ++ntask) { p->h_order[k++] = (uint32_t)i; p->h_order[k++] = (uint32_t)(i + 1 < cnt ? i + 1 : i); }
@@ -1744,9 +1757,10 @@ int ksw2amd_plan_describe(const ksw2amd_plan_t *p, char *buf, int cap)
 		const int G = k->solo ? 64 : k->pk ? k2a_pkcfg_G[k->cfg] : k2a_cfg_G[k->cfg], C = k->solo ? 2 * K2A_SOLO_ROWS(k->mode == K2A_MODE_SCORE) : k->pk ? k2a_pkcfg_C[k->cfg] : k2a_cfg_C[k->cfg];
 		const int form = k->defer ? 3 : k->solo ? 0 : k->pk ? (k->cfg == K2A_PKCFG_MP ? 0 : k2a_shim_pk_form(k->cfg, p->dual, k->mode, k->nomax, k->count))
 		                                     : (k->cfg == K2A_CFG_MP ? k2a_shim_mp_form(p->dual, k->mode, k->count) : 0);
-		len += snprintf(buf + len, (size_t)(cap - len), "kernel=%s G=%d C=%d gaps=%d mode=%s rebased=%d nomax=%d generic=%d form=%s tasks=%d uniform=%d wire4=%d tn=%d\n",
+		len += snprintf(buf + len, (size_t)(cap - len), "kernel=%s G=%d C=%d gaps=%d mode=%s rebased=%d nomax=%d generic=%d form=%s tasks=%d uniform=%d wire4=%d tn=%d base=%d\n",
 		                kind, G, C, p->dual ? 2 : 1, mode_name[k->mode], k->rb, k->nomax, k->generic, form_name[form], k->count, p->uni ? 1 : 0,
-		                p->up_state ? p->up_state->wire4 : 0, (k->pk || k->solo) && k->sc.pk_tn1 ? 1 : 0);      /* tn: target wildcards are rows of this packed class (K2aScoring.pk_tn1) */
+		                p->up_state ? p->up_state->wire4 : 0, (k->pk || k->solo) && k->sc.pk_tn1 ? 1 : 0,       /* tn: target wildcards are rows of this packed class (K2aScoring.pk_tn1) */
+		                (k->pk || k->solo) ? k->sc.pk_base : 0);                                                /* base: what the class's profile bytes are short of (K2aScoring.pk_base) */
 	}
 	return p->ncls;
 }

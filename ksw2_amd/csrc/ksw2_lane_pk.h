@@ -42,6 +42,18 @@
  * The query's wildcard (code 4) is table entry 4.  A TARGET code of 4 has no byte in a four-byte profile: such pairs take the
  * int32 kernels (the host's scan finds them; kernels of unscanned plans report them, K2aLanePk::seen).
  *
+ * Open form (K2A_HL_OPEN, ksw2_types.h; default): the row registers hl[] -- and with them the ports hout / hin / hd0 / hu_prev, the
+ * checkpoint stream's hin and K2aCkHead.hd0, the generation-serial boundary rows -- hold H - q, the value t the gap states are opened
+ * from, instead of H.  H itself is a transient of the step; its only later reader was the row below, one step on, which formed
+ * H + (smax + e) from it while t = H - q sat in a register anyway.  With t kept, that row's candidate is
+ *     t(i-1,j-1) + v_perm_b32(cpB, cpA, selector[row]),      byte = q + e + s(t, q)   (K2aScoring.cp; first-piece q in the two-piece kernels)
+ * : two instructions, and the v_add_u32 of the bias is gone from every row of every packed fill.  E, F, the transient H, the row
+ * maxima and the books mean what they meant, and t is a value the loop formed before, so no range changes.  Whoever reads hl or a
+ * port as a score adds q back (k2a_hl_q): the border rows and corners of do_init / start_high, top_inputs, the strip epilogues behind
+ * stage_rows (which stages the rows as they are), fin_score_only.  A scoring whose bytes do not fit 0..255 (a score below -(q + e),
+ * or q + e + smax > 255) stores them less K2aScoring.pk_base and runs the TN build, whose slow path adds the constant: k2a_tn_fix.
+ * -DK2A_HL_OPEN=0 builds the form described above (H in hl, penalty bytes), for A/B libraries.
+ *
  * Preconditions, checked by the host (ksw2_host_plan.c::pk_eligible / pk_window_ok): m <= 5, no wildcard code in the TARGET, gap
  * costs and smax + e non-negative, and every in-band H, E, F provably inside (-16384 + max(q+e, q2+e2), 12287 - max(q+e, q2+e2))
  * so that -16384 can stand for -infinity (K2A_PK_VMAX = 12287 is the largest value the offset form holds, ksw2_types.h).
@@ -194,11 +206,29 @@ K2A_FN uint32_t k2a_tsel_wild(uint32_t x)
 	const uint32_t n = x & 0x00040004u;
 	return ((x ^ n) + K2A_TSEL_BASE) | n | (n << 1);
 }
-K2A_FN k2a_pk k2a_tn_fix(k2a_pk cand, uint32_t sel, int tn1)
+/* Open form: the slow path is also where a scoring whose bytes do not fit as they are (K2aScoring.pk_base != 0) gets the constant
+ * back that its bytes are short of -- every row; a wildcard row adds pk_tnc for the byte it did not take.  Both are signed: packed adds */
+K2A_FN k2a_pk k2a_tn_fix(k2a_pk cand, uint32_t sel, const K2aScoring &sc)
 {
 	const uint32_t m = (sel >> 3) & 0x00010001u;                  /* 1 per half that holds a wildcard row */
-	return cand - m * ((uint32_t)(tn1 - 1) & 0xffu);              /* both halves with one 32-bit subtract (k2a_sub32: the low half does not borrow) */
+#if K2A_HL_OPEN
+	return k2a_pk_add(k2a_pk_add(cand, k2a_pk2(sc.pk_base)), m * ((uint32_t)sc.pk_tnc & 0xffffu));
+#else
+	return cand - m * ((uint32_t)(sc.pk_tn1 - 1) & 0xffu);        /* both halves with one 32-bit subtract (k2a_sub32: the low half does not borrow) */
+#endif
 }
+/* Which builds of a lane carry the slow path.  On the device: the TN build only -- the kernels pick it for a wavefront-task whose
+ * targets hold a wildcard, and for every task of a scoring with pk_base != 0 (ksw2_shim_hip.hip), and the plain build has neither a
+ * test nor an instruction for it.  Host builds of the lane code (the simulator, the stand-alone checkers) pick their body by the
+ * targets alone, so there both builds carry it: a scoring with pk_base != 0 sets hasn in do_init whatever the build, whoever drives
+ * the lanes ORs it into wn, and the candidates get the constant.  With pk_base = 0 the host's plain build never enters it. */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define K2A_TN_PATH(TN) (TN)
+#else
+#define K2A_TN_PATH(TN) true
+#endif
+/* the constant between H and what the row registers hold (Open form, below) */
+K2A_FN int k2a_hl_q(const K2aScoring &sc) { return K2A_HL_OPEN ? sc.q : 0; }
 
 /* Direction flags of one row for both halves (traceback kernels, round 5).  Every decision of the reference's direction logic
  * (ksw2_extz.c:72-86 / 98-112, ksw2_extd.c:88-114 / 126-152) is the SIGN of a packed difference: s1..s4 = candidate - gap state in
@@ -412,7 +442,7 @@ struct K2aLanePk {
 		 * alignment A's code with alignment B's and one add turns the pair into the row's selector -- this code runs with one lane
 		 * per group active, every 17-19 steps: it was 11 % of the kernel when it went byte by byte. */
 		const uint8_t *tpa = ta + (size_t)S * C, *tpb = tbq + (size_t)S * C;
-		hasn = 0;
+		hasn = (K2A_TN_PATH(TN) && K2A_HL_OPEN && sc.pk_base != 0) ? 1u : 0u;      /* bytes short of pk_base: every row takes the slow path */
 #pragma unroll
 		for (int c4 = 0; c4 < C; c4 += 4) {
 			uint32_t da, db;
@@ -434,10 +464,11 @@ struct K2aLanePk {
 			if (!NOMAX) set_rmax(c, neg);                        /* the arg-max column is written with the row's first live cell */
 		}
 		const int hcorner = k2a_border<DUAL>(sc, i0) + sc.e * (i0 - 1);   /* H(i0-1,-1), carrying the bias of row i0-1 */
+		const int hq = k2a_hl_q(sc);                                      /* hl, hd0, hu_prev hold H - hq */
 		if (forced) { baseA = forced->baseA; baseB = forced->baseB; delta = 0; }
 		else if (RB) {
 			/* new base = the diagonal input of the strip's first cell; hu_prev is still relative to the base above */
-			const int nbA = js == 0 ? hcorner : bsA + k2a_pk_lo(k2a_ofs_off(hu_prev)), nbB = js == 0 ? hcorner : bsB + k2a_pk_hi(k2a_ofs_off(hu_prev));
+			const int nbA = js == 0 ? hcorner : bsA + hq + k2a_pk_lo(k2a_ofs_off(hu_prev)), nbB = js == 0 ? hcorner : bsB + hq + k2a_pk_hi(k2a_ofs_off(hu_prev));
 			delta = S == 0 ? 0u : k2a_pair16((uint32_t)(bsA - nbA) & 0xffffu, (uint32_t)(bsB - nbB) & 0xffffu);
 			baseA = nbA; baseB = nbB;
 		}
@@ -450,16 +481,16 @@ struct K2aLanePk {
 				for (int c = 0; c < C; ++c) {                    /* ksw2_extz.c:43-44, ksw2_extd.c:49-52; row bias e*i */
 					const int hb = k2a_border<DUAL>(sc, i0 + c + 1) + sc.e * (i0 + c);
 					if (i0 + c <= w) {
-						hl[c] = k2a_ofs_on(k2a_pair16((uint32_t)(hb - baseA) & 0xffffu, (uint32_t)(hb - baseB) & 0xffffu));
-						f[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e));
-						if (DUAL) f2[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2));
+						hl[c] = k2a_ofs_on(k2a_pair16((uint32_t)(hb - hq - baseA) & 0xffffu, (uint32_t)(hb - hq - baseB) & 0xffffu));
+						f[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e - hq));
+						if (DUAL) f2[c] = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2 - hq));
 					}
 				}
 			}
 		}
 		if (forced) hd0 = forced->hd0;
-		else if (RB) hd0 = K2A_OFS;                             /* 0 by construction of the base */
-		else if (js == 0) hd0 = k2a_pku(hcorner);
+		else if (RB) hd0 = k2a_pku(-hq);                        /* H = 0 by construction of the base */
+		else if (js == 0) hd0 = k2a_pku(hcorner - hq);
 		else hd0 = hu_prev;
 		Snext += G;
 		schedule_next();
@@ -471,7 +502,7 @@ struct K2aLanePk {
 		if (S == 0) {
 			const int hb = k2a_border<DUAL>(sc, k - koff + 1);
 			const k2a_pk h0 = k2a_ofs_on(k2a_pair16((uint32_t)(hb - baseA) & 0xffffu, (uint32_t)(hb - baseB) & 0xffffu));
-			hin = k2a_pk_sub(h0, k2a_pk2(sc.e));               /* row -1 carries bias -e, E(0,.) and E~(0,.) bias 0 */
+			hin = k2a_pk_sub(h0, k2a_pk2(sc.e + k2a_hl_q(sc)));  /* row -1 carries bias -e (and the port holds H - q), E(0,.) and E~(0,.) bias 0 */
 			ein = k2a_pk_sub(h0, k2a_pk2(sc.q + sc.e)); e2in = k2a_pk_sub(h0, k2a_pk2(sc.q2 + sc.e2));
 		}
 	}
@@ -495,7 +526,9 @@ struct K2aLanePk {
 		const int dd = k - kd;                                 /* jj - i0 */
 		const k2a_pk neg = k2a_pku(K2A_NEG16);
 		const k2a_pk gq = k2a_pk2(sc.q), ge = k2a_pk2(sc.e), gq2 = k2a_pk2(sc.q2), ge2 = k2a_pk2(sc.e2), de2 = k2a_pk2(sc.e2 - sc.e);
+#if !K2A_HL_OPEN
 		const k2a_pk bias = k2a_pk2(sc.pk_smax + sc.e);        /* largest score + row-bias step; the rows subtract their penalties from it */
+#endif
 		k2a_pk e = ein, e2 = e2in;
 		if (dd >= wup) { e = neg; e2 = neg; }                  /* the cell above is outside the band */
 		rp.begin(dd, w, rows_m1);
@@ -513,12 +546,17 @@ struct K2aLanePk {
 			for (int r = 0; r < CH; ++r) {
 				const int c = c0 + r;
 				const k2a_pk up = r == 0 ? above_old : hl[c - 1];
+#if K2A_HL_OPEN
+				/* (H - q)(i-1,j-1) + q + s(i,j) + e: the row's bytes { q + e + s(tA, qA), 0, q + e + s(tB, qB), 0 } out of the column profiles */
+				cand[r] = k2a_add32(up, k2a_perm(cpB, cpA, tc(c)));
+#else
 				/* H(i-1,j-1) + s(i,j) + e: the row's penalty bytes { smax - s(tA, qA), 0, smax - s(tB, qB), 0 } out of the column profiles */
 				cand[r] = k2a_sub32(k2a_add32(up, bias), k2a_perm(cpB, cpA, tc(c)));
+#endif
 			}
-			if (TN && wn) {                                      /* a target wildcard row somewhere in the wavefront (scalar test): its constant penalty */
+			if (K2A_TN_PATH(TN) && wn) {                                      /* a target wildcard row somewhere in the wavefront (scalar test): its constant; or bytes short of pk_base */
 #pragma unroll
-				for (int r = 0; r < CH; ++r) cand[r] = k2a_tn_fix(cand[r], tc(c0 + r), sc.pk_tn1);
+				for (int r = 0; r < CH; ++r) cand[r] = k2a_tn_fix(cand[r], tc(c0 + r), sc);
 			}
 			above_old = last_old;
 			if (CH < C) K2A_SCHED_FENCE();
@@ -573,7 +611,7 @@ struct K2aLanePk {
 						else uprev = u;
 					} else tbw[c >> 1] = k2a_perm(fl, dprev, 0x05040100u);               /* bytes {A(c-1), B(c-1), A(c), B(c)} */
 				}
-				hl[c] = h;
+				hl[c] = K2A_HL_OPEN ? t : h;                       /* what the row below starts from next step */
 			}
 			if (CH < C) K2A_SCHED_FENCE();
 		}
@@ -634,7 +672,7 @@ struct K2aLanePk {
 	K2A_FN void stage_rows(uint32_t *rowbuf) const
 	{
 #pragma unroll
-		for (int c = 0; c < C; ++c) { rowbuf[c] = k2a_ofs_off(hl[c]); rowbuf[C + c] = k2a_ofs_off(rmax(c)); rowbuf[2 * C + c] = rmj(c); }   /* plain int16 halves */
+		for (int c = 0; c < C; ++c) { rowbuf[c] = k2a_ofs_off(hl[c]); rowbuf[C + c] = k2a_ofs_off(rmax(c)); rowbuf[2 * C + c] = rmj(c); }   /* plain int16 halves; the H column as hl holds it (H - q: its readers add k2a_hl_q) */
 		rowbuf[3 * C] = (uint32_t)i0;
 		if (RB) { rowbuf[3 * C + 1] = (uint32_t)baseA; rowbuf[3 * C + 2] = (uint32_t)baseB; }
 	}
@@ -657,7 +695,7 @@ struct K2aLanePk {
 				if (i < tlen && !bdrop) {
 					const bool reach = i + w >= qlen - 1;
 					const int unb = (half ? baseB : baseA) - sc.e * i;                                       /* plus base, minus row bias */
-					const int hend = (int)(int16_t)(rowbuf[c] >> sh) + unb, H = (int)(int16_t)(rowbuf[C + c] >> sh) + unb;
+					const int hend = (int)(int16_t)(rowbuf[c] >> sh) + k2a_hl_q(sc) + unb, H = (int)(int16_t)(rowbuf[C + c] >> sh) + unb;
 					const int j = (int)(uint16_t)(rowbuf[2 * C + c] >> sh);             /* column index: unsigned, reads up to 65 000 */
 					if (reach && hend > bmqe) { bmqe = hend; bmqe_t = i; }
 					if (i == tlen_full - 1) { bmte = H; bmte_q = j; }
@@ -744,7 +782,7 @@ struct K2aLanePk {
 			const k2a_pk bias = k2a_pk2(sc.e * i);
 			const k2a_pk pj = rowbuf[2 * C + c], ipk = k2a_pk2(i);
 			/* un-bias; rows past the target end hold -inf, which must stay below every real score */
-			const k2a_pk ph = (i < tlen) ? k2a_pk_sub(rowbuf[c], bias) : k2a_pk2(K2A_NEG16);
+			const k2a_pk ph = (i < tlen) ? k2a_pk_sub(rowbuf[c], k2a_pk2(sc.e * i - k2a_hl_q(sc))) : k2a_pk2(K2A_NEG16);
 			const k2a_pk pm = (i < tlen) ? k2a_pk_sub(rowbuf[C + c], bias) : k2a_pk2(K2A_NEG16);
 			/* rows past the target end kept rmax = hl = -inf and can never win */
 			const k2a_pk up = k2a_pk_sign(k2a_pk_sub(lmax, pm));                /* max < H */
@@ -769,8 +807,8 @@ struct K2aLanePk {
 			k2a_pk v = 0;
 #pragma unroll
 			for (int c = 0; c < C; ++c) if (i0 + c == last) v = k2a_ofs_off(hl[c]);
-			bA->score = k2a_pk_lo(v) + (RB ? baseA : 0) - sc.e * last;
-			bB->score = k2a_pk_hi(v) + (RB ? baseB : 0) - sc.e * last;
+			bA->score = k2a_pk_lo(v) + k2a_hl_q(sc) + (RB ? baseA : 0) - sc.e * last;
+			bB->score = k2a_pk_hi(v) + k2a_hl_q(sc) + (RB ? baseB : 0) - sc.e * last;
 		}
 		end_strip();
 	}
@@ -791,7 +829,7 @@ K2A_FN void k2a_fin_rows_half(const K2aScoring &sc, K2aBook *b, int zdrop, const
 		if (i < tlen && !bdrop) {
 			const bool reach = i + w >= qlen - 1;
 			const int unb = base - sc.e * i;                                                        /* plus base, minus row bias */
-			const int hend = (int)(int16_t)(rowbuf[c] >> sh) + unb, H = (int)(int16_t)(rowbuf[C + c] >> sh) + unb;
+			const int hend = (int)(int16_t)(rowbuf[c] >> sh) + k2a_hl_q(sc) + unb, H = (int)(int16_t)(rowbuf[C + c] >> sh) + unb;
 			const int j = (int)(uint16_t)(rowbuf[2 * C + c] >> sh);
 			if (reach && hend > bmqe) { bmqe = hend; bmqe_t = i; }
 			if (i == tlen_full - 1) { bmte = H; bmte_q = j; }

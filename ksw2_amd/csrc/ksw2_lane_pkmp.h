@@ -15,6 +15,10 @@
  * arriving from the lane above is taken as -inf when it is below K2A_PKMP_DEAD before the difference of the two lanes'
  * bases is added (a finished or not yet started lane's base is arbitrary).
  *
+ * Open form (ksw2_lane_pk.h): the rows, the ports and the boundary arrays' H hold H - q like every packed lane's.  Nothing here reads
+ * them as scores but do_fin: `rebase` centres on the largest value of hl as it is (the base then sits q lower, which the bases carry
+ * along), `adopt` and `shift` send a dead value to -16384 in either form, and P.delta is a difference of bases.
+ *
  * Schedule: generation g = strips g*64 .. g*64+63 over all their in-band columns (k2a_gen_cols, ksw2_lane.h), lane l skewed
  * by l steps.  The bottom row of a generation goes to the next one through a boundary array in HBM as packed values plus
  * the producing lane's bases (16 bytes per column); different generations of one pair run on different wavefronts of a
@@ -174,7 +178,7 @@ struct K2aLanePkMp {
 				if (i < P.tlen && !bdrop) {
 					const bool reach = i + P.w >= P.qlen - 1;
 					const unsigned long long key = k2a_key_load(&spill[2 * c + half]);
-					const int hend = (int)(int16_t)(rowbuf[c] >> sh) + base - sc.e * i;
+					const int hend = (int)(int16_t)(rowbuf[c] >> sh) + k2a_hl_q(sc) + base - sc.e * i;      /* hl holds H - q (ksw2_lane_pk.h, "Open form") */
 					const int H = (int)((uint32_t)(key >> 32) ^ 0x80000000u) - sc.e * i;
 					const int j = FIRSTJ ? 0xffff - (int)(key & 0xffffu) : (int)(key & 0xffffu);
 					if (reach && hend > bmqe) { bmqe = hend; bmqe_t = i; }

@@ -132,7 +132,7 @@ struct K2aLaneSolo {
 		const k2a_pk neg = k2a_pku(K2A_NEG16);
 		/* target codes of the 2C rows as selectors into the step's column profiles (ksw2_lane_pk.h), low half = rows i0.., high
 		 * half = rows i0+C..: four rows of both halves per pair of dwords */
-		hasn = 0;
+		hasn = (K2A_TN_PATH(TN) && K2A_HL_OPEN && sc.pk_base != 0) ? 1u : 0u;      /* bytes short of pk_base: every row takes the slow path (K2aLanePk::do_init) */
 #pragma unroll
 		for (int c4 = 0; c4 < C; c4 += 4) {
 			const uint32_t da = tnA[c4 / 4], db = tnB[c4 / 4];             /* prefetch_next(), one strip ago */
@@ -150,26 +150,27 @@ struct K2aLaneSolo {
 		for (int c = 0; c < C; ++c) { hl[c] = neg; f[c] = neg; if (DUAL) f2[c] = neg; rmax[c] = neg; rmj[c] = 0; }
 		/* base = the diagonal input of the low half's first cell */
 		const int hcorner = k2a_border<DUAL>(sc, i0) + sc.e * (i0 - 1);
-		const int nb = js == 0 ? hcorner : bs + k2a_pk_hi(k2a_ofs_off(hu_prev));          /* what arrived: the high half of the lane above */
+		const int hq = k2a_hl_q(sc);                                                      /* hl, hd0, hu_prev and the half-exchange hold H - hq (ksw2_lane_pk.h, "Open form") */
+		const int nb = js == 0 ? hcorner : bs + hq + k2a_pk_hi(k2a_ofs_off(hu_prev));     /* what arrived: the high half of the lane above */
 		delta = D == 0 ? 0u : ((uint32_t)(bs - nb) & 0xffffu);                            /* high half: 0 until start_high() */
 		baseA = nb;
 		if (i0 <= w) {                                          /* rows starting at column 0: virtual column -1 (ksw2_extz.c:43-44) */
 #pragma unroll
 			for (int c = 0; c < C; ++c) {
 				const int ha = k2a_border<DUAL>(sc, i0 + c + 1) + sc.e * (i0 + c);
-				const uint32_t va = i0 + c <= w ? k2a_h16(ha - baseA) : k2a_h16(K2A_NEG16);
+				const uint32_t va = i0 + c <= w ? k2a_h16(ha - hq - baseA) : k2a_h16(K2A_NEG16);
 				hl[c] = k2a_pair16(va, neg >> 16);
-				const k2a_pk fl = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e));
+				const k2a_pk fl = k2a_pk_sub(hl[c], k2a_pk2(sc.q + sc.e - hq));
 				f[c] = k2a_pair16(i0 + c <= w ? fl & 0xffffu : neg & 0xffffu, neg >> 16);
 				if (DUAL) {
-					const k2a_pk fl2 = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2));
+					const k2a_pk fl2 = k2a_pk_sub(hl[c], k2a_pk2(sc.q2 + sc.e2 - hq));
 					f2[c] = k2a_pair16(i0 + c <= w ? fl2 & 0xffffu : neg & 0xffffu, neg >> 16);
 				}
 			}
 		}
 		/* diagonal input of the low half's first cell: 0 by construction of the base.  The high half takes the low half's bottom
 		 * row one step later: start_high() gives it its own base just before its first step. */
-		hd0 = k2a_pair16(k2a_h16(0), neg >> 16);
+		hd0 = k2a_pair16(k2a_h16(-hq), neg >> 16);
 		qw = qn0 << qn_sh;                                      /* this strip's first group of query codes */
 		Dnext += G;
 		schedule_next();
@@ -184,7 +185,7 @@ struct K2aLaneSolo {
 	 * earlier and the steps in between, which run the high half dead, would wipe them). */
 	K2A_FN void start_high(const K2aScoring &sc)
 	{
-		const int i0b = i0 + C;
+		const int i0b = i0 + C, hq = k2a_hl_q(sc);
 		if (i0b <= w) {
 			const uint32_t negh = (uint32_t)k2a_h16(K2A_NEG16);
 			baseB = k2a_border<DUAL>(sc, i0b) + sc.e * (i0b - 1);
@@ -192,7 +193,7 @@ struct K2aLaneSolo {
 			for (int c = 0; c < C; ++c) {
 				const bool in = i0b + c <= w;
 				const int hb = k2a_border<DUAL>(sc, i0b + c + 1) + sc.e * (i0b + c) - baseB;
-				const uint32_t vb = in ? k2a_h16(hb) : negh;
+				const uint32_t vb = in ? k2a_h16(hb - hq) : negh;
 				const uint32_t fb = in ? k2a_h16(hb - (sc.q + sc.e)) : negh;
 				hl[c] = (hl[c] & 0xffffu) | (vb << 16);
 				f[c] = (f[c] & 0xffffu) | (fb << 16);
@@ -201,8 +202,8 @@ struct K2aLaneSolo {
 					f2[c] = (f2[c] & 0xffffu) | (fb2 << 16);
 				}
 			}
-		} else baseB = baseA + k2a_pk_hi(k2a_ofs_off(hd0));
-		hd0 = (hd0 & 0xffffu) | ((uint32_t)k2a_h16(0) << 16);
+		} else baseB = baseA + hq + k2a_pk_hi(k2a_ofs_off(hd0));
+		hd0 = (hd0 & 0xffffu) | ((uint32_t)k2a_h16(-hq) << 16);
 		delta = (delta & 0xffffu) | (((uint32_t)(baseA - baseB) & 0xffffu) << 16);
 	}
 
@@ -211,7 +212,7 @@ struct K2aLaneSolo {
 	{
 		if (D == 0) {
 			const int hb = k2a_border<DUAL>(sc, k - koff + 1) - baseA;
-			const uint32_t h0 = k2a_h16(hb - sc.e), e0 = k2a_h16(hb - (sc.q + sc.e));
+			const uint32_t h0 = k2a_h16(hb - sc.e - k2a_hl_q(sc)), e0 = k2a_h16(hb - (sc.q + sc.e));
 			const uint32_t e20 = k2a_h16(hb - (sc.q2 + sc.e2));
 			hin = (hin & 0xffff0000u) | h0; ein = (ein & 0xffff0000u) | e0; e2in = (e2in & 0xffff0000u) | e20;
 		}
@@ -225,7 +226,9 @@ struct K2aLaneSolo {
 		const int ddA = k - kd, ddB = ddA - C - 1;
 		const k2a_pk neg = k2a_pku(K2A_NEG16);
 		const k2a_pk gq = k2a_pk2(sc.q), ge = k2a_pk2(sc.e), gq2 = k2a_pk2(sc.q2), ge2 = k2a_pk2(sc.e2), de2 = k2a_pk2(sc.e2 - sc.e);
+#if !K2A_HL_OPEN
 		const k2a_pk bias = k2a_pk2(sc.pk_smax + sc.e);        /* largest score + row-bias step; the rows subtract their penalties from it */
+#endif
 		/* the cell above is outside the band: per half */
 		const k2a_pk cut = k2a_pair16(ddA >= wupA ? 0xffffu : 0u, ddB >= w ? 0xffffu : 0u);
 		k2a_pk e = k2a_pk_sel(cut, neg, ein), e2 = DUAL ? k2a_pk_sel(cut, neg, e2in) : 0u;
@@ -249,11 +252,15 @@ struct K2aLaneSolo {
 #pragma unroll
 			for (int r = 0; r < CH; ++r) {
 				const int c = c0 + r;
+#if K2A_HL_OPEN
+				cand[r] = k2a_add32(r == 0 ? above_old : hl[c - 1], k2a_perm(cpB, cpA, tc[c]));      /* (H - q) + { q + e + s }: K2aLanePk::step_rows */
+#else
 				cand[r] = k2a_sub32(k2a_add32(r == 0 ? above_old : hl[c - 1], bias), k2a_perm(cpB, cpA, tc[c]));
+#endif
 			}
-			if (TN && wn) {                                          /* a target wildcard row somewhere in the wavefront (K2aLanePk::step) */
+			if (K2A_TN_PATH(TN) && wn) {                                          /* a target wildcard row somewhere in the wavefront (K2aLanePk::step) */
 #pragma unroll
-				for (int r = 0; r < CH; ++r) cand[r] = k2a_tn_fix(cand[r], tc[c0 + r], sc.pk_tn1);
+				for (int r = 0; r < CH; ++r) cand[r] = k2a_tn_fix(cand[r], tc[c0 + r], sc);
 			}
 			above_old = last_old;
 			if (CH < C) K2A_SCHED_FENCE();
@@ -295,7 +302,7 @@ struct K2aLaneSolo {
 					if (c & 1) tbw[c >> 1] = k2a_perm(fl, dprev, 0x05040100u);
 					else dprev = fl;
 				}
-				hl[c] = h;
+				hl[c] = K2A_HL_OPEN ? t : h;
 			}
 			if (CH < C) K2A_SCHED_FENCE();
 		}
@@ -354,7 +361,7 @@ struct K2aLaneSolo {
 			if (i < tlen && !bdrop) {
 				const bool reach = i + w >= qlen - 1;
 				const int unb = (c < C ? baseA : baseB) - sc.e * i;
-				const int hend = (int)(int16_t)rowbuf[c] + unb, H = (int)(int16_t)rowbuf[2 * C + c] + unb;
+				const int hend = (int)(int16_t)rowbuf[c] + k2a_hl_q(sc) + unb, H = (int)(int16_t)rowbuf[2 * C + c] + unb;      /* the staged H column is hl's: H - q */
 				const int j = (int)(uint16_t)rowbuf[4 * C + c];
 				if (reach && hend > bmqe) { bmqe = hend; bmqe_t = i; }
 				if (i == tlen_full - 1) { bmte = H; bmte_q = j; }

@@ -581,7 +581,7 @@ k2a_fill_pk_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const
 		const uint64_t m1 = __builtin_amdgcn_ballot_w64((scan & 1u) != 0), m2 = __builtin_amdgcn_ballot_w64((scan & 2u) != 0);
 		const uint64_t gm = (G == 64 ? ~0ull : (1ull << (G & 63)) - 1) << (grp * G);
 		scan = ((m1 & gm) ? 1u : 0u) | ((m2 & gm) ? 2u : 0u);
-		if (m1 != 0)
+		if (m1 != 0 || sc.pk_base != 0)                        /* pk_base: the bytes of sc.cp are short of a constant that only the TN build adds (K2aScoring) */
 			k2a_fill_pk_body<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, true>(sc, pairs, order2, ntasks, seq, tb, res, wt, wave, lane, grp, gl, scan_on, scan, book, stage[wave], lrows, cptab, tbstage, tbruns);
 		else
 			k2a_fill_pk_body<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, false>(sc, pairs, order2, ntasks, seq, tb, res, wt, wave, lane, grp, gl, scan_on, scan, book, stage[wave], lrows, cptab, tbstage, tbruns);
@@ -911,7 +911,7 @@ k2a_fill_solo_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, con
 	}
 	const bool any4 = __builtin_amdgcn_ballot_w64((scan & 1u) != 0) != 0;
 	scan = (any4 ? 1u : 0u) | (__builtin_amdgcn_ballot_w64((scan & 2u) != 0) != 0 ? 2u : 0u);
-	if (any4) k2a_fill_solo_body<C, DUAL, MODE, true>(sc, pairs, order, ntasks, seq, tb, res, task, wave, lane, scan_on, scan, book, stage, cptab, tbstage, tbruns);
+	if (any4 || sc.pk_base != 0) k2a_fill_solo_body<C, DUAL, MODE, true>(sc, pairs, order, ntasks, seq, tb, res, task, wave, lane, scan_on, scan, book, stage, cptab, tbstage, tbruns);
 	else k2a_fill_solo_body<C, DUAL, MODE, false>(sc, pairs, order, ntasks, seq, tb, res, task, wave, lane, scan_on, scan, book, stage, cptab, tbstage, tbruns);
 }
 
@@ -1347,7 +1347,7 @@ k2a_fill_pkmp_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, con
 		const K2aPair pa = pairs[order2[2 * task]], pb = pairs[order2[2 * task + 1]];
 		scan = k2a_scan_codes<64>(seq + pa.toff, pa.tlen_full, lane) | k2a_scan_codes<64>(seq + pb.toff, pb.tlen_full, lane);
 	}
-	if (__builtin_amdgcn_ballot_w64((scan & 1u) != 0) != 0)
+	if (__builtin_amdgcn_ballot_w64((scan & 1u) != 0) != 0 || sc.pk_base != 0)
 		k2a_fill_pkmp_body<DUAL, MODE, true>(sc, pairs, order2, ntasks, seq, tb, bnd, res, task, wave, lane, book, rowbuf, pstart, pcount, tbstage, tbruns, cptab);
 	else
 		k2a_fill_pkmp_body<DUAL, MODE, false>(sc, pairs, order2, ntasks, seq, tb, bnd, res, task, wave, lane, book, rowbuf, pstart, pcount, tbstage, tbruns, cptab);

@@ -46,6 +46,12 @@
 #define K2A_PKMP_DEAD (-8192)       /* relative values below this are -inf */
 #define K2A_PKMP_RMAX_LIMIT 10000   /* a window's row maximum further above the base than this is merged into its key; it may drift
                                      * K2A_PKMP_T steps further before the next check and must still fit K2A_PK_VMAX */
+/* what the row registers of the packed kernels hold (ksw2_lane_pk.h, "Open form"): 1 = H - q and the profile bytes of K2aScoring.cp
+ * carry q + e + s; 0 = H and penalties below smax, the form before (A/B libraries: tools/scripts/ab_libs.sh).  Here, so that the host's
+ * table and the device's reading of it cannot disagree */
+#ifndef K2A_HL_OPEN
+#define K2A_HL_OPEN 1
+#endif
 #define K2A_PK_NIBBLES(C, dual) (!(dual) && (C) == 16)
 #define K2A_PK_TB_BYTES(C, dual) (K2A_PK_NIBBLES(C, dual) ? (C) : 2 * (C))        /* per lane-step: C rows x 2 alignments */
 
@@ -54,9 +60,13 @@ typedef struct K2aScoring {
 	int32_t q, e, q2, e2;        /* gap open / extend; (q2,e2) only for the two-piece model, q+e <= q2+e2 */
 	uint32_t prof[5];            /* prof[t] = bytes { s(t,0), s(t,1), s(t,2), s(t,3) } for target code t   */
 	int32_t colw[5];             /* colw[t] = s(t, 4): score against the query wildcard (code 4)          */
-	/* packed-int16 kernels (ksw2_lane_pk.h, "column profiles"): any matrix over codes 0..3 x 0..4 as penalties below its largest
-	 * entry.  cp[q] = bytes { smax - s(0,q), smax - s(1,q), smax - s(2,q), smax - s(3,q) } for query code q (4 = the query's
-	 * wildcard; 5..7 unused, zero); the diagonal candidate is H + (pk_smax + e) - byte t of cp[q]: one v_perm_b32 per row. */
+	/* packed-int16 kernels (ksw2_lane_pk.h, "column profiles"): any matrix over codes 0..3 x 0..4, one byte per score.  The rows keep
+	 * H - q (K2A_HL_OPEN: the value the gap states are opened from), so the byte carries everything the diagonal adds to it:
+	 * cp[q] = bytes { q + e + s(t, q) - pk_base, t = 0..3 } for query code q (4 = the query's wildcard; 5..7 unused, zero), and the
+	 * diagonal candidate is (H - q)(i-1,j-1) + byte t of cp[q]: one v_perm_b32 and one add per row.  pk_base (below) is 0 for every
+	 * scoring whose bytes fit 0..255 as they are.
+	 * -DK2A_HL_OPEN=0, the form before: cp[q] = bytes { smax - s(t, q) }, penalties below the matrix's largest entry, and the
+	 * candidate is H + (pk_smax + e) - byte. */
 	uint32_t cp[8];
 	int32_t pk_smax;
 	/* TARGET wildcard (code 4) in the packed kernels (round 6): where its scores do not depend on the query code -- s(4, q) = sN for q =
@@ -66,6 +76,11 @@ typedef struct K2aScoring {
 	int32_t pk_tn1;
 	int32_t m;                   /* residue types; m > 5: scores come from `mat` (staged in LDS), prof/colw unused */
 	const int8_t *mat;           /* device copy of the effective m x m matrix, mat[target*m + query]       */
+	/* K2A_HL_OPEN: what the bytes of cp are short of q + e + s -- 0 unless a score lies below -(q + e) or q + e + smax above 255; then
+	 * the signed constant that brings every byte into 0..255 (smax - smin <= 255 always fits).  A scoring with pk_base != 0 runs the TN
+	 * build of every packed body, whose wavefront-uniform slow path adds it to the candidates (K2aLanePk::step_rows); the device's plain
+	 * build never looks at it (host builds: K2A_TN_PATH, ksw2_lane_pk.h).  pk_tnc: what a TARGET wildcard row (pk_tn1 != 0; profile byte 0) adds instead of a byte: q + e + sN - pk_base */
+	int32_t pk_base, pk_tnc;
 } K2aScoring;
 
 /* register window classes of the diagonal-major kernel: K slots of 64 target positions hold diagonals of up to
