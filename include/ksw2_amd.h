@@ -517,6 +517,10 @@ ksw2amd_plan_t *ksw2amd_extf_plan_create(int8_t mch, int8_t mis, int8_t e, int n
 /* raw device results without the host-side ez[] assembly: 16 int32 per pair
  * {max, zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, reach_end, n_cigar, rows_done, ti, tj, 0, 0} */
 int  ksw2amd_plan_fetch_raw(ksw2amd_plan_t *plan, int32_t *out16);
+/* diagnostics: the plan's output buffers back to what a freshly created plan may hold -- result records zeroed, traceback and CIGAR
+ * scratch filled with 0xA5 bytes; sequences, pair records, task lists and the boundary scratch stay.  A run after it has to produce
+ * every record again (tests of repeated runs).  Works on the plan's last stream and synchronises it. */
+int  ksw2amd_plan_scrub(ksw2amd_plan_t *plan);
 
 #ifdef __cplusplus
 }

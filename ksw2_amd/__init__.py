@@ -102,7 +102,7 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_last_error", "ksw2amd_backend", "ksw2amd_device_count", "ksw2amd_set_device", "ksw2amd_release_cache",
            "ksw2amd_extz_batch", "ksw2amd_extd_batch", "ksw2amd_plan_create", "ksw2amd_plan_run", "ksw2amd_plan_fetch",
            "ksw2amd_plan_destroy", "ksw2amd_plan_timing", "ksw2amd_plan_cells", "ksw2amd_plan_device_bytes", "ksw2amd_plan_packed_pairs",
-           "ksw2amd_plan_fetch_raw", "ksw_exts2_sse", "ksw_exts2_sse41", "ksw_exts2_sse2", "ksw2amd_exts_batch", "ksw2amd_exts_plan_create",
+           "ksw2amd_plan_fetch_raw", "ksw2amd_plan_scrub", "ksw_exts2_sse", "ksw_exts2_sse41", "ksw_exts2_sse2", "ksw2amd_exts_batch", "ksw2amd_exts_plan_create",
            "ksw_extf2_sse", "ksw2amd_extf_batch", "ksw2amd_extf_plan_create",
            "ksw2amd_set_devices", "ksw2amd_set_error_handler", "ksw2amd_error_count", "ksw2amd_host_stats",
            "ksw2amd_set_sse_compat", "ksw2amd_sse_plan_create", "ksw2amd_plan_describe", "ksw2amd_reload_env",
@@ -217,6 +217,7 @@ class Library:
         L.ksw2amd_plan_packed_pairs.argtypes = [ctypes.c_void_p]
         L.ksw2amd_plan_packed_pairs.restype = ctypes.c_int64
         L.ksw2amd_plan_fetch_raw.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+        L.ksw2amd_plan_scrub.argtypes = [ctypes.c_void_p]
         L.ksw2amd_set_devices.argtypes = [_int, ctypes.POINTER(_int)]
         L.ksw2amd_set_error_handler.argtypes = [ERROR_FN, ctypes.c_void_p]
         L.ksw2amd_set_error_handler.restype = None
@@ -1085,6 +1086,10 @@ class Plan:
         out = np.zeros((max(self.b.n, 1), 16), dtype=np.int32)
         self.L._check(self.L.lib.ksw2amd_plan_fetch_raw(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return out[:self.b.n]
+
+    def scrub(self):
+        """ksw2amd_plan_scrub: result records zeroed, traceback and CIGAR scratch filled with 0xA5; the next run() has to write them all."""
+        self.L._check(self.L.lib.ksw2amd_plan_scrub(self.h))
 
     def close(self):
         if self.h:

@@ -1827,6 +1827,32 @@ int ksw2amd_plan_fetch_raw(ksw2amd_plan_t *p, int32_t *out16)
 	return KSW2AMD_OK;
 }
 
+/* diagnostics (tests of repeated runs): the plan's OUTPUT buffers back to what a freshly created plan may hold,
+ * so that a run that does nothing cannot pass for one that repeated the last run's records.  d_res: zero, as create (splice, X-drop,
+ * SSE-compatible plans) or the first run (clear_res) leave it.  d_tb and d_cig: 0xA5 bytes -- cache_get hands out recycled buffers,
+ * their contents are arbitrary at create.  Nothing of either is left out: no create-time upload of the four plan kinds writes into
+ * d_res, d_tb or d_cig (plan_create_ex, ksw2amd_exts_plan_create, ksw2amd_extf_plan_create, ksw2amd_sse_plan_create upload d_seq,
+ * d_pairs, d_order, the watermark block and the queue descriptors only); what lives in d_tb besides traceback bytes is written by the
+ * run itself: the frozen-book list (its counter by the DEFER fill, K2A_ZLIST_WORDS in front of the class's first block), the strip
+ * checkpoints, the X-drop lane class's state rows (zeroed by every extf_plan_run) and the X-drop HBM form's state (initialised by its
+ * kernel).  Untouched: d_seq, d_pairs, d_order, d_wm with the queue descriptors, and d_bnd -- no run after the first refills the
+ * boundary scratch, which is the state a repeated run has to live with.  On the plan's last stream, which is synchronised. */
+int ksw2amd_plan_scrub(ksw2amd_plan_t *p)
+{
+	void *st;
+	if (!p) return fail(KSW2AMD_E_PARAM, "plan_scrub: NULL plan%s", 0);
+	if (p->gather && gather_wait(p)) return fail(KSW2AMD_E_NODEVICE, "plan_scrub: upload failed: %s", k2a_shim_last_error());
+	if (p->reject_all || p->ntasks == 0 || !p->d_res) return KSW2AMD_OK;
+	st = p->stream;
+	if ((p->stream_used && k2a_shim_stream_sync(st)) ||
+	    k2a_shim_memset(p->d_res, 0, sizeof(K2aResult) * (size_t)p->n, st) ||
+	    (p->d_tb && k2a_shim_memset(p->d_tb, 0xA5, p->tb_bytes, st)) ||
+	    (p->d_cig && k2a_shim_memset(p->d_cig, 0xA5, p->cig_words * 4, st)) ||
+	    k2a_shim_stream_sync(st))
+		return fail(KSW2AMD_E_NODEVICE, "plan_scrub: %s", k2a_shim_last_error());
+	return KSW2AMD_OK;
+}
+
 /* M runs -> =/X runs (KSW_EZ_EQX, ksw2_extd2_sse.c:399-406 / ksw2.h:163-182) */
 /* `stride` = 1 for plain sequences, 2 for the byte-interleaved copies of a packed task (pointer already at the right half) */
 void eqx_rewrite(void *km, const uint8_t *query, const uint8_t *target, int stride, ksw_extz_t *ez)
