@@ -430,7 +430,8 @@ int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape
  * without a positive entry is legal here (the local entries skip such pairs; these do not).  Every argument and every code is checked
  * before anything is staged or launched (KSW2AMD_E_PARAM); the flat entry checks the codes on the device, chunk by chunk, and has the
  * chunking, reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat.
- * Not computed: the two-piece gap cost, free query ends, a suboptimal score (the start tb and a CIGAR: ksw2amd_sg_align_batch below).
+ * Not computed: free query ends, a suboptimal score (the start tb and a CIGAR: ksw2amd_sg_align_batch below; the two-piece gap cost:
+ * ksw2amd_sgd_batch further below).
  * ksw2amd_sg: one pair on a ksw_ll_qinit profile; returns the score, equal to row 0 of ksw2amd_sg_batch on that pair.  On a device
  * failure or a bad argument it returns 0 with *qe = *te = -1 and reports like ksw_ll_i16 (ksw2amd_error_count, ksw2amd_last_error, the
  * handler, KSW2AMD_ABORT_ON_ERROR). */
@@ -463,12 +464,44 @@ int ksw2amd_sg(void *q, int tlen, const uint8_t *target, int gapo, int gape, int
  * intervals come back once for the CIGAR stage; on a failure every aln[] entry holds score 0, coordinates -1, n_cigar 0).
  * ksw2amd_sg_align: one pair on a ksw_ll_qinit profile; returns the score; on a failure 0 with those reset values, reported like
  * ksw_ll_i16.  Device failures: a negative code, no CPU fallback.
- * Not computed, here either: the two-piece gap cost, free query ends, a suboptimal score. */
+ * Not computed, here either: free query ends, a suboptimal score (the two-piece gap cost: ksw2amd_sgd_align_batch below). */
 int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
                            const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
 int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
                                 const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
 int ksw2amd_sg_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int flag, ksw2amd_laln_t *aln);
+
+/* Semi-global alignment under the two-piece gap cost of ksw_extd (new): the six entries above with
+ * (gapo2, gape2) after gape, as in the ksw2amd_lld_* entries.  A gap of length l >= 1 costs
+ *   cost(l) = min(gapo + l * gape, gapo2 + l * gape2),
+ * the cost of the reference's scalar ksw_extd, which never swaps or orders the two pieces; neither do these entries.
+ * Score and te: H(t, -1) = 0 for every t >= -1, H(-1, j) = -cost(j + 1), H = max(diag + s, E, F, E2, F2) with the four Gotoh states of
+ *   ksw_extd, -infinity on the boundary, NO clamp at 0; score = max over t of H(t, qlen - 1), te the smallest such t, qe = qlen - 1.
+ *   Nothing is launched for qlen <= 0 -> (0, -1, -1), nor for tlen <= 0 with qlen > 0 -> (-cost(qlen), qlen - 1, -1).
+ * Range: the four costs 0..127; m 1..127 for the score entries, 2..127 for ksw2amd_sgd_align_batch / _flat and ksw2amd_sgd_align (the CIGAR
+ *   stage is the scalar ksw_extd, which aligns nothing with m = 1: KSW2AMD_E_PARAM, as for ksw2amd_lld_align_batch); every residue code < m;
+ *   a pair with cost(qlen) + (qlen + 1) * smax > 0x3fffffff, smax = max(0, largest matrix entry), is KSW2AMD_E_PARAM.
+ * tb, qb and the CIGAR (the align entries): as for ksw2amd_sg_align_batch with G(x) taken under the scalar ksw_extd (w = -1, zdrop = -1) and
+ *   G(te + 1) = -cost(qlen): tb is the LARGEST x in [0, te + 1] with G(x) == score, the empty interval (tb = te + 1) wins its ties, qb = 0.
+ *   In the reference's terms: with r = ksw_extd(reverse(query), reverse(target[0..te]), w = -1, zdrop = -1, KSW_EZ_SCORE_ONLY),
+ *   (score, te) is the best max(r.mqe, -cost(qlen)) at the smallest te, and tb = te - r.mqe_t when r.mqe > -cost(qlen), te + 1 otherwise.
+ *   The CIGAR of a non-empty interval is exactly that of the scalar ksw_extd(km, qlen, query, te-tb+1, target+tb, m, mat, gapo, gape, gapo2,
+ *   gape2, -1, -1, KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)), &ez), whose score equals `score` (checked for every
+ *   pair; a mismatch is reported as an error, never returned); of an empty interval, qlen I.  flag: KSW_EZ_SCORE_ONLY, KSW_EZ_RIGHT,
+ *   KSW_EZ_REV_CIGAR; any other bit is KSW2AMD_E_PARAM.  tlen <= 0 with qlen > 0: score -cost(qlen), qb 0, qe qlen - 1, te -1, tb 0, and the
+ *   CIGAR qlen I unless KSW_EZ_SCORE_ONLY.
+ * Equal pieces: with (gapo2, gape2) = (gapo, gape), or with gapo2 >= gapo and gape2 >= gape, every field of every result equals the
+ *   corresponding ksw2amd_sg_* entry's.
+ * Everything else is as for the ksw2amd_sg_* entries: every argument checked before anything is staged or launched, flat chunking, the
+ * on-device code check, the reset values on a failure, on_device arenas, no CPU fallback, KSW2AMD_LL_FORM / KSW2AMD_LL_LDS /
+ * KSW2AMD_LL_CHUNK_BYTES; the single-pair entries report failures like ksw_ll_i16.
+ * Not computed: free query ends, a suboptimal score. */
+int ksw2amd_sgd_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
+int ksw2amd_sgd_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
+int ksw2amd_sgd(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int *qe, int *te);
+int ksw2amd_sgd_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+int ksw2amd_sgd_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
+int ksw2amd_sgd_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int flag, ksw2amd_laln_t *aln);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

@@ -115,7 +115,9 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
            "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
            "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
-           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align"]
+           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
+           "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
+           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -128,7 +130,9 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_lld_batch", "ksw2amd_lld_align_batch", "ksw2amd_lld_batch_flat", "ksw2amd_lld_align_batch_flat",
                 "ksw2amd_lld_sub_batch", "ksw2amd_lld_sub_batch_flat", "ksw2amd_lld", "ksw2amd_lld_align", "ksw2amd_lld_sub",
                 "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
-           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align"]
+           "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
+           "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
+           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align"]
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -292,6 +296,13 @@ class Library:
             L.ksw2amd_sg_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
             L.ksw2amd_sg_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
             L.ksw2amd_sg_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_sgd_batch"):         # (nor the two-piece semi-global entries and their launches' twin: tests/sgd_util.py adds them)
+            L.ksw2amd_sgd_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_sgd_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_sgd.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+            L.ksw2amd_sgd_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_sgd_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_sgd_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -801,6 +812,85 @@ class Library:
         try:
             a = LocalAln()
             score = self.lib.ksw2amd_sg_align(None, prof, len(ta), tp, gapo, gape, flag, ctypes.byref(a))
+        finally:
+            _libc.free(prof)
+        d = self._aln_to_dict(a)
+        assert d["score"] == int(score)
+        return d
+
+    # ---- the same under the two-piece gap cost min(gapo + l * gape, gapo2 + l * gape2) of ksw_extd, the pieces in the caller's order
+    def sgd_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, m=None, pairs=None, n=None):
+        """ksw2amd_sgd_batch: sg_batch under the two-piece gap cost -> (n, 3) int32 array of score, qe (= qlen - 1), te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        rc = self.lib.ksw2amd_sgd_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, n, pairs,
+                                        out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def sgd_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, m=None, device_base=None, out=None):
+        """ksw2amd_sgd_batch_flat: sgd_batch on an arena (see ll_batch_flat) -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1] == 3
+        rc = self.lib.ksw2amd_sgd_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, n, ctypes.byref(f),
+                                             out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def sgd(self, query, target, mat, gapo, gape, gapo2, gape2, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_sgd -> (score, qe, te)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw2amd_sgd(prof, len(ta), tp, gapo, gape, gapo2, gape2, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
+
+    def sgd_align_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, flag=0, m=None, pairs=None, n=None, aln=None):
+        """ksw2amd_sgd_align_batch(km=NULL, ...): sg_align_batch under the two-piece gap cost (the CIGAR is the scalar ksw_extd's) -> list of
+        dicts score, qb (0), qe, tb, te, n_cigar, cigar."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_sgd_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, flag, n, pairs, aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def sgd_align_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, flag=0, m=None, device_base=None, aln=None):
+        """ksw2amd_sgd_align_batch_flat(km=NULL, ...): sgd_align_batch on an arena (see ll_batch_flat) -> list of dicts."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        rc = self.lib.ksw2amd_sgd_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, gapo2, gape2, flag, n, ctypes.byref(f), aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def sgd_align(self, query, target, mat, gapo, gape, gapo2, gape2, flag=0, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_sgd_align(km=NULL, ...) -> dict like sgd_align_batch's."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            a = LocalAln()
+            score = self.lib.ksw2amd_sgd_align(None, prof, len(ta), tp, gapo, gape, gapo2, gape2, flag, ctypes.byref(a))
         finally:
             _libc.free(prof)
         d = self._aln_to_dict(a)

@@ -328,15 +328,17 @@ typedef struct {
  * ksw2_host_sga.o name it.  With it (never with sb or du) a chunk runs every pair with rows = target on biased values: smax is max(0, largest
  * entry), the packed form is admitted by ll_sg_pk_admit, a pair without a query or without a target gets its corner result instead of being
  * skipped, and a matrix without a positive entry still launches.  With a rev as well (ksw2_host_sga.c): rev is
- * k2a_shim_launch_sg_rev, the anchored start pass, which only ksw2_host_sga.o names */
+ * k2a_shim_launch_sg_rev, the anchored start pass, which only ksw2_host_sga.o names.  With an ll_dual_t as well (ksw2_host_sgd.c, DESIGN.md
+ * section 3.22): launch = k2a_shim_launch_sgd and rev = k2a_shim_launch_sgd_rev, which only ksw2_host_sgd.o names; the ll_dual_t's fwd is not
+ * called and may be NULL */
 typedef struct {
 	ll_fwd_fn launch;
 } ll_fit_t;
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft);
 size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit);
-int ll_sg_pk_admit(int qlen, int gapo, int gape, int smax);
-int ll_sg_check_range(int i, int qlen, int gapo, int gape, int smax);
+int ll_sg_pk_admit(int qlen, int gapo, int gape, const ll_dual_t *du, int smax);      /* du: cost(qlen) of the two pieces */
+int ll_sg_check_range(int i, int qlen, int gapo, int gape, const ll_dual_t *du, int smax);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
@@ -353,5 +355,16 @@ int lla_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int fla
                  const ll_dual_t *du);
 int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln, ll_rev_fn rev,
                  const ll_dual_t *du);
+/* the stages of ksw2amd_sg_align_batch behind the two kernel passes (ksw2_host_sga.c), and the two batch entries with their launches
+ * and the two-piece cost as parameters (ksw2_host_sgd.c) */
+void sga_reset(int n, ksw2amd_laln_t *aln);
+int sga_check_flag(int flag);
+int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);
+int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln,
+               const ll_dual_t *du);      /* du: the scalar ksw_extd with (gapo2, gape2) instead of ksw_extz */
+int sga_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln,
+                 const ll_fit_t *ft, ll_rev_fn rev, const ll_dual_t *du);
+int sga_align_flat_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln,
+                      const ll_fit_t *ft, ll_rev_fn rev, const ll_dual_t *du);
 #pragma GCC visibility pop
 #endif

@@ -11,7 +11,7 @@
  * function pointer, so this object never refers to k2a_shim_launch_ll_rev (the simulator builds of tests/ll_util.py link it without one).
  * The two-piece entries (ksw2_host_lld.c, ksw2_host_llds.c) hand in their forward, start-cell and profile-writing launches and the second
  * gap pair the same way (ll_dual_t), and the semi-global entries (ksw2_host_sg.c; with the start pass as the ll_rev_fn: ksw2_host_sga.c)
- * their launch and mode (ll_fit_t).
+ * their launch and mode (ll_fit_t); the two-piece semi-global entries (ksw2_host_sgd.c) hand in both an ll_fit_t and an ll_dual_t.
  */
 #include "ksw2_host_int.h"
 
@@ -29,17 +29,25 @@ static int ll_pk_admit(int qlen, int tlen, int smax)
  * largest value the packed step forms, H'(t - 1, j - 1) + smax, stays within B + qlen * smax + smax.  The packed form is exact while that
  * fits 16 bits: B + (qlen + 1) * smax <= 65535.  (No column index is kept in 16 bits: the maximum is over the last column only.)
  * With smax = 127 and costs (5, 1): 128 * qlen + 132 <= 65535, a query of 510 is packed and one of 511 is not. */
-int ll_sg_pk_admit(int qlen, int gapo, int gape, int smax)
+/* du (ksw2amd_sgd_batch): B = cost(qlen), the smaller of the two pieces -- the bound is exact because B is the min */
+static int64_t ll_sg_cost(int l, int gapo, int gape, const ll_dual_t *du)
 {
-	return (int64_t)gapo + (int64_t)qlen * gape + ((int64_t)qlen + 1) * smax <= 65535;
+	const int64_t a = (int64_t)gapo + (int64_t)l * gape, b = du ? (int64_t)du->gapo2 + (int64_t)l * du->gape2 : a;
+	return a < b ? a : b;
 }
 
-/* ... and in int32 while gapo + qlen * (gape + smax) + smax <= 0x3fffffff (pair i of the call, for the message) */
-int ll_sg_check_range(int i, int qlen, int gapo, int gape, int smax)
+int ll_sg_pk_admit(int qlen, int gapo, int gape, const ll_dual_t *du, int smax)
+{
+	return ll_sg_cost(qlen, gapo, gape, du) + ((int64_t)qlen + 1) * smax <= 65535;
+}
+
+/* ... and in int32 while gapo + qlen * (gape + smax) + smax <= 0x3fffffff (pair i of the call, for the message); du: cost(qlen) + (qlen + 1) * smax */
+int ll_sg_check_range(int i, int qlen, int gapo, int gape, const ll_dual_t *du, int smax)
 {
 	char msg[32];
-	if (qlen <= 0 || (int64_t)gapo + (int64_t)qlen * ((int64_t)gape + smax) + smax <= 0x3fffffff) return KSW2AMD_OK;
+	if (qlen <= 0 || ll_sg_cost(qlen, gapo, gape, du) + ((int64_t)qlen + 1) * smax <= 0x3fffffff) return KSW2AMD_OK;
 	snprintf(msg, sizeof(msg), "%d", i);
+	if (du) return fail(KSW2AMD_E_PARAM, "semi-global alignment: pair %s: cost(qlen) + (qlen + 1) * smax exceeds 0x3fffffff", msg);
 	return fail(KSW2AMD_E_PARAM, "semi-global alignment: pair %s: gapo + qlen * (gape + smax) + smax exceeds 0x3fffffff", msg);
 }
 
@@ -113,13 +121,13 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
 }
 
 /* semi-global mode: the pairs of a chunk that launch nothing and still have a result -- a query without a target */
-static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2amd_lres_t *res, K2aLLBeg *beg)
+static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const ll_dual_t *du, ksw2amd_lres_t *res, K2aLLBeg *beg)
 {
 	int i;
 	for (i = 0; i < n; ++i) {
 		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
 		if (ql > 0 && tl <= 0) {                                 /* the whole query inserted before the target */
-			res[i].score = -(gapo + ql * gape); res[i].qe = ql - 1; res[i].te = -1;
+			res[i].score = -(int)ll_sg_cost(ql, gapo, gape, du); res[i].qe = ql - 1; res[i].te = -1;
 			if (beg) { beg[i].score = res[i].score; beg[i].qb = 0; beg[i].tb = 0; }      /* (rev: the empty interval, tb = te + 1) */
 		}
 	}
@@ -143,7 +151,10 @@ static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, ksw2a
  * ft->launch, smax is max(0, largest entry) and may be 0, the packed form is admitted by ll_sg_pk_admit, and a pair without a query or
  * without a target gets its corner result (ll_fit_corners) once the chunk has passed its checks, instead of being skipped
  * ft with rev: ksw2amd_sg_align_batch (ksw2_host_sga.c) -- rev is the caller's anchored start pass; beg[i] = its
- * score, 0, tb (te + 1 for the empty interval), a corner pair's filled in with its result; the trace lines say "sga" */
+ * score, 0, tb (te + 1 for the empty interval), a corner pair's filled in with its result; the trace lines say "sga"
+ * ft and du together (never with sb): ksw2amd_sgd_batch and, with rev, ksw2amd_sgd_align_batch (ksw2_host_sgd.c) --
+ * the forward launch is ft->launch (du->fwd is not called), par.oe2 / ge2 and the 16-byte boundary come from du, the corners, the packed
+ * admission and the range check use cost(qlen) = min of the two pieces; the trace lines say "sgd" / "sgda" */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft)
 {
@@ -151,7 +162,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
 	const ll_fwd_fn fwd = ft ? ft->launch : du ? du->fwd : k2a_shim_launch_ll;
-	const char *tn = ft ? (rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
+	const char *tn = ft ? (du ? (rev ? "sgda" : "sgd") : rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
@@ -174,7 +185,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		s.rows = imax(ql, tl); s.cols = imin(ql, tl); s.sw = ql > tl; s.idx = (uint32_t)i;
 		if (sb || ft) { s.rows = tl; s.cols = ql; s.sw = 0; }    /* row maxima (ft: the last column) are per target position only if rows = target */
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
-		if (form > 0 && (ft ? ll_sg_pk_admit(ql, gapo, gape, smax) : ll_pk_admit(ql, tl, smax) && s.cols <= 65535)) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
+		if (form > 0 && (ft ? ll_sg_pk_admit(ql, gapo, gape, du, smax) : ll_pk_admit(ql, tl, smax) && s.cols <= 65535)) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
 		else i32[ni32++] = s;
 	}
 	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
@@ -200,7 +211,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] %s-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers", sb->excl,
 	                              du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
-	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, res, rev ? beg : 0); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
+	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, du, res, rev ? beg : 0); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
@@ -314,7 +325,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		for (i = 0; i < ni32; ++i) memcpy(&sub[i32[i].idx], &hs[i32[i].idx], sizeof(K2aLLSub));
 	}
 done:
-	if (ft) ll_fit_corners(src, n, gapo, gape, res, rev ? beg : 0);
+	if (ft) ll_fit_corners(src, n, gapo, gape, du, res, rev ? beg : 0);
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);
@@ -340,7 +351,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 		const ksw2amd_lpair_t *p = &pairs[i];
 		char msg[96];
 		if ((p->qlen > 0 && !p->query) || (p->tlen > 0 && !p->target)) { snprintf(msg, sizeof(msg), "%d", i); return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: NULL sequence", msg); }
-		if (ft && (rc = ll_sg_check_range(i, p->qlen, gapo, gape, smax)) != KSW2AMD_OK) return rc;
+		if (ft && (rc = ll_sg_check_range(i, p->qlen, gapo, gape, du, smax)) != KSW2AMD_OK) return rc;
 		if ((p->qlen > 0 && ll_bad_code(p->query, p->qlen, m)) || (p->tlen > 0 && ll_bad_code(p->target, p->tlen, m))) {
 			snprintf(msg, sizeof(msg), "%d", i);
 			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: residue code >= m", msg);

@@ -51,7 +51,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 			snprintf(msg, sizeof(msg), "%d", i);
 			return fail(KSW2AMD_E_PARAM, "local alignment: pair %s: query and target lie more than 4 GiB apart in the arena", msg);
 		}
-		if (ft && (rc = ll_sg_check_range(i, in->qlen[i], gapo, gape, smax)) != KSW2AMD_OK) return rc;
+		if (ft && (rc = ll_sg_check_range(i, in->qlen[i], gapo, gape, du, smax)) != KSW2AMD_OK) return rc;
 	}
 	if (n == 0) return KSW2AMD_OK;
 	if (k2a_shim_device_count() <= 0) return fail(KSW2AMD_E_NODEVICE, "no usable %s device", k2a_shim_backend());      /* the check runs there whatever the matrix */

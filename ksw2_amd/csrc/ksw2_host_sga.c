@@ -11,10 +11,12 @@
  *      empty interval's CIGAR, qlen I, is written here.
  *
  * This is the only host object that refers to k2a_shim_launch_sg_rev (it names k2a_shim_launch_sg too, like ksw2_host_sg.c).
+ * The two-piece entries (ksw2_host_sgd.c) run the same three stages through sga_align_ex / sga_align_flat_ex with
+ * their own two launches and an ll_dual_t: stage 3 is then the scalar-contract ksw_extd.
  */
 #include "ksw2_host_int.h"
 
-static void sga_reset(int n, ksw2amd_laln_t *aln)
+void sga_reset(int n, ksw2amd_laln_t *aln)
 {
 	int i;
 	for (i = 0; aln && i < n; ++i) { aln[i].score = 0; aln[i].qb = aln[i].qe = aln[i].tb = aln[i].te = -1; aln[i].n_cigar = 0; }
@@ -24,7 +26,7 @@ static inline int sga_has_interval(const ksw2amd_laln_t *a) { return a->qe >= 0 
 
 /* after stages 1 and 2: aln[i] = score, the query's ends and the interval, the start pass checked against the forward pass (no CIGAR
  * yet).  qlen / tlen: the pairs' lengths, `stride` ints apart.  Returns through *na the pairs with a non-empty interval */
-static int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na_)
+int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na_)
 {
 	int i, na = 0;
 	char msg[96];
@@ -48,8 +50,10 @@ static int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t str
 
 /* stage 3.  Empty intervals: qlen I, written here.  The na pairs with an interval: query x target[tb..te] as extension pairs into HOST
  * memory; the caller's CIGAR buffers travel through ez[] and back.  at_start = 0: pairs[i].target is the full target; 1: it already points
- * at residue tb (the intervals of a device arena, brought back).  pairs[i].query is the whole query either way */
-static int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln)
+ * at residue tb (the intervals of a device arena, brought back).  pairs[i].query is the whole query either way.  du: the scalar ksw_extd
+ * with (gapo2, gape2), the pieces in the caller's order, instead of ksw_extz */
+int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln,
+               const ll_dual_t *du)
 {
 	ksw2amd_pair_t *pp = 0;
 	ksw_extz_t *ez = 0;
@@ -84,8 +88,8 @@ static int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, in
 	}
 	{
 		ksw2amd_scoring_t sc;
-		sc.m = m; sc.mat = mat; sc.q = (int8_t)gapo; sc.e = (int8_t)gape; sc.q2 = 0; sc.e2 = 0;
-		rc = ext_batch_scalar(0, km, &sc, na, pp, ez);
+		sc.m = m; sc.mat = mat; sc.q = (int8_t)gapo; sc.e = (int8_t)gape; sc.q2 = (int8_t)(du ? du->gapo2 : 0); sc.e2 = (int8_t)(du ? du->gape2 : 0);
+		rc = ext_batch_scalar(du != 0, km, &sc, na, pp, ez);
 	}
 	for (k = 0; k < na; ++k) {                 /* the buffers may have grown or moved: always hand them back */
 		ksw2amd_laln_t *a = &aln[idx[k]];
@@ -102,17 +106,18 @@ out:
 	return rc;
 }
 
-static int sga_check_flag(int flag)
+int sga_check_flag(int flag)
 {
 	if (flag & ~LLA_FLAGS) return fail(KSW2AMD_E_PARAM, "semi-global alignment: flag accepts KSW_EZ_SCORE_ONLY, KSW_EZ_RIGHT and KSW_EZ_REV_CIGAR only%s", "");
 	return KSW2AMD_OK;
 }
 
-int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+/* ksw2amd_sg_align_batch with the two launches (ft->launch, rev) and the two-piece cost (du, or NULL) as parameters */
+int sga_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln,
+                 const ll_fit_t *ft, ll_rev_fn rev, const ll_dual_t *du)
 {
 	ksw2amd_lres_t *res = 0;
 	K2aLLBeg *beg = 0;
-	ll_fit_t ft;
 	int na = 0, rc;
 	/* every argument before anything is staged: the flag here, m / mat / gap costs / pair array / ranges / residue codes in ll_batch_ex */
 	if ((rc = sga_check_flag(flag)) != KSW2AMD_OK) return rc;
@@ -122,25 +127,32 @@ int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gap
 		beg = (K2aLLBeg*)malloc(sizeof(*beg) * (size_t)n);
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
 	}
-	ft.launch = k2a_shim_launch_sg;
-	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, k2a_shim_launch_sg_rev, beg, 0, 0, 0, &ft)) != KSW2AMD_OK) goto out;
+	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, rev, beg, 0, 0, du, ft)) != KSW2AMD_OK) goto out;
 	if (n == 0) goto out;
 	if ((rc = sga_cells(n, &pairs[0].qlen, &pairs[0].tlen, sizeof(pairs[0]) / sizeof(int32_t), res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if (flag & KSW_EZ_SCORE_ONLY) goto out;
-	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln);
+	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln, du);
 out:
 	if (rc != KSW2AMD_OK) sga_reset(n, aln);
 	free(res); free(beg);
 	return rc;
 }
 
-int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
+int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
+{
+	ll_fit_t ft;
+	ft.launch = k2a_shim_launch_sg;
+	return sga_align_ex(km, m, mat, gapo, gape, flag, n, pairs, aln, &ft, k2a_shim_launch_sg_rev, 0);
+}
+
+/* ksw2amd_sg_align_batch_flat, parameterised the same way */
+int sga_align_flat_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln,
+                      const ll_fit_t *ft, ll_rev_fn rev, const ll_dual_t *du)
 {
 	ksw2amd_lres_t *res = 0;
 	K2aLLBeg *beg = 0;
 	ksw2amd_lpair_t *pp = 0;
 	uint8_t *host = 0;
-	ll_fit_t ft;
 	int i, na = 0, rc;
 	if ((rc = sga_check_flag(flag)) != KSW2AMD_OK) return rc;
 	if (n > 0 && !aln) return fail(KSW2AMD_E_PARAM, "semi-global alignment: bad flat batch arguments%s", "");
@@ -150,12 +162,11 @@ int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, in
 		if (!res || !beg) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
 	}
 	/* stages 1 and 2 on the borrowed arena */
-	ft.launch = k2a_shim_launch_sg;
-	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, k2a_shim_launch_sg_rev, beg, 0, 0, 0, &ft)) != KSW2AMD_OK) goto out;
+	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, rev, beg, 0, 0, du, ft)) != KSW2AMD_OK) goto out;
 	if (n == 0) goto out;
 	if ((rc = sga_cells(n, in->qlen, in->tlen, 1, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if (flag & KSW_EZ_SCORE_ONLY) goto out;
-	/* stage 3: the whole query x [toff + tb, toff + te] under the scalar ksw_extz contract.  Host arena: pointers into it.  Device arena: the
+	/* stage 3: the whole query x [toff + tb, toff + te] under the scalar ksw_extz (du: ksw_extd) contract.  Host arena: pointers into it.  Device arena: the
 	 * span of the aligned intervals and their queries comes back in one copy, then the same pointer path */
 	pp = (ksw2amd_lpair_t*)malloc(sizeof(*pp) * (size_t)n);
 	if (!pp) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
@@ -183,11 +194,18 @@ int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, in
 		for (i = 0; i < n; ++i) {                 /* (a device arena without an interval: the pointers are never followed) */
 			pp[i].query = in->base + in->qoff[i]; pp[i].target = in->base + in->toff[i]; pp[i].qlen = in->qlen[i]; pp[i].tlen = in->tlen[i];
 		}
-	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pp, in->on_device != 0, na, aln);
+	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pp, in->on_device != 0, na, aln, du);
 out:
 	if (rc != KSW2AMD_OK) sga_reset(n, aln);
 	free(res); free(beg); free(pp); free(host);
 	return rc;
+}
+
+int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
+{
+	ll_fit_t ft;
+	ft.launch = k2a_shim_launch_sg;
+	return sga_align_flat_ex(km, m, mat, gapo, gape, flag, n, in, aln, &ft, k2a_shim_launch_sg_rev, 0);
 }
 
 /* one pair on a ksw_ll_qinit profile: entry 0 of ksw2amd_sg_align_batch, failures reported like ksw_ll_i16 */

@@ -101,7 +101,7 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * length l: a second pair of gap states E2 / F2 under (oe2, ge2) beside E / F, clamped at 0 like them (max(0, .., max(X, 0)) = max(0, .., X),
  * and max(H - oe, max(X, 0) - ge, 0) = max(max(H - oe, X - ge), 0) because -ge <= 0: H never sees the clamp), f2[] per row and
  * an e2 chain down the strip that reaches the lane below (and the boundary) with H and E.  With DUAL = false nothing of it exists. */
-/* FIT (rows = target, never with SUB / DUAL): the semi-global mode of ksw2amd_sg_batch -- the whole query
+/* FIT (rows = target, never with SUB; with DUAL: below): the semi-global mode of ksw2amd_sg_batch -- the whole query
  * against the best interval of the target, no clamp at 0.  With B = gapo + ncols * gape every true H(t, j) >= -(gapo + (j + 1) * gape) >= -B
  * (insert the query up to column j), so the cell update runs unchanged on H' = H + B >= 0; E' and F' held clamped at 0 stand for values
  * <= -B, which reach an H only where H = -B itself.  What differs is the boundary -- column -1 is B in every row (H(t, -1) = 0), row -1 is
@@ -112,7 +112,11 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * the reversed target prefix that ends in the forward pass's row te, anchored at (te, ncols - 1) and free to end in any row.  Row i holds
  * r[te - i] (rl = te + 1), column j holds c[ncols - 1 - j] (cl = ncols for every half).  Row -1 is fit_top as it stands; column -1 is the
  * global boundary H'(i, -1) = B - (gapo + (i + 1) * gape) = (ncols - 1 - i) * gape held at 0 (fit_left) where the forward pass has B.  The key
- * starts at (0, row -1): H'(-1, ncols - 1) = 0 is the empty interval, and k2a_ll_better lets it win its ties. */
+ * starts at (0, row -1): H'(-1, ncols - 1) = 0 is the empty interval, and k2a_ll_better lets it win its ties.
+ * FIT with DUAL (with and without REV): the same two passes under the two-piece cost of ksw2amd_sgd_batch / ksw2amd_sgd_align_batch
+ * (DESIGN.md section 3.22).  cost(l) = min(gapo + l * gape, gapo2 + l * gape2), the pieces as the caller orders them; B = cost(ncols), row -1
+ * is B - cost(j + 1) with E' and E2' opened from it, column -1 of the reverse pass is max(B - cost(i + 1), 0), and F2' of column 0 is opened
+ * from column -1 like F'.  cost() is non-decreasing, so cost(j + 1) <= B and the arguments above carry over; step() is DUAL's as it stands. */
 template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
@@ -147,6 +151,7 @@ struct K2aLaneLL {
 		for (int h = 0; h < NH; ++h) k2a_ll_key_reset(key[h]);
 		if (FIT) {
 			bias = (uint32_t)(par.oe - par.ge + ncols * par.ge) * x;
+			if (DUAL) bias = (uint32_t)k2a_min(par.oe - par.ge + ncols * par.ge, par.oe2 - par.ge2 + ncols * par.ge2) * x;      /* cost(ncols) */
 			if (!REV) for (int h = 0; h < NH; ++h) key[h].s = -1;      /* REV: (0, -1), row -1 of the last column */
 		}
 	}
@@ -159,9 +164,24 @@ struct K2aLaneLL {
 		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u);
 	}
 
-	/* FIT with REV: column -1 of row i, H'(i, -1) = max(ncols - 1 - i, 0) * gape (i = -1: B) */
+	/* FIT with DUAL: cost(l), l >= 1, from the lane's copies of the four costs */
+	K2A_FN int fit_cost(int l) const
+	{
+		const uint32_t mk = PK ? 0xffffu : 0xffffffffu;
+		return k2a_min((int)(oe & mk) + (l - 1) * (int)(ge & mk), (int)(oe2 & mk) + (l - 1) * (int)(ge2 & mk));
+	}
+	/* ... row -1 of column k: H'(-1, k) = B - cost(k + 1), E'(0, k) = sat(H' - oe), E2'(0, k) = sat(H' - oe2) */
+	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e, uint32_t &e2) const
+	{
+		const uint32_t mk = PK ? 0xffffu : 0xffffffffu;
+		const int v = fit_bias() - fit_cost(k + 1), w = k2a_max(v - (int)(oe & mk), 0), w2 = k2a_max(v - (int)(oe2 & mk), 0);
+		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u); e2 = (uint32_t)w2 * (PK ? 0x10001u : 1u);
+	}
+
+	/* FIT with REV: column -1 of row i, H'(i, -1) = max(ncols - 1 - i, 0) * gape (i = -1: B); DUAL: max(B - cost(i + 1), 0) */
 	K2A_FN uint32_t fit_left(int i) const
 	{
+		if (DUAL) return i < 0 ? bias : (uint32_t)k2a_max(fit_bias() - fit_cost(i + 1), 0) * (PK ? 0x10001u : 1u);
 		return i < 0 ? bias : (uint32_t)(k2a_max(ncols - 1 - i, 0) * (int)(ge & (PK ? 0xffffu : 0xffffffffu))) * (PK ? 0x10001u : 1u);
 	}
 
@@ -183,7 +203,7 @@ struct K2aLaneLL {
 			}
 			hl[c] = !FIT ? 0u : REV ? fit_left(i) : bias; rmax[c] = 0; rcol[c] = 0;
 			f[c] = !(FIT && REV) ? f0 : PK ? k2a_ll_subs(hl[c], oe) : (uint32_t)k2a_max((int)hl[c] - (int)oe, 0);      /* F'(i, 0) = sat(H'(i, -1) - oe) */
-			if (DUAL) f2[DUAL ? c : 0] = 0;
+			if (DUAL) f2[DUAL ? c : 0] = !FIT ? 0u : PK ? k2a_ll_subs(hl[c], oe2) : (uint32_t)k2a_max((int)hl[c] - (int)oe2, 0);      /* FIT: F2'(i, 0) = sat(H'(i, -1) - oe2) */
 			if (LDSP) {
 				pa[c] = a * (uint32_t)m;
 				if (PK) pb[c] = b * (uint32_t)m;

@@ -218,6 +218,14 @@ int k2a_shim_launch_sg(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
  * have no such symbol). */
 int k2a_shim_launch_sg_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+/* The same two launches under the two-piece gap cost of ksw2amd_sgd_batch / ksw2amd_sgd_align_batch (par->oe2 / ge2; DESIGN.md section
+ * 3.22): the same grids, H' = H + cost(ncols) with cost(l) = min(gapo + l * gape, gapo2 + l * gape2), and 16 bytes of boundary per column
+ * at scratch + tasks[].boff (16-byte aligned) for tasks over K2A_LL_ROWS rows.  Packed tasks take the LDS profile whatever `lds` says unless
+ * K2A_SGD_PK_REG.  Only ksw2_host_sgd.c calls them (the other simulator builds have no such symbols). */
+int k2a_shim_launch_sgd(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream);
+int k2a_shim_launch_sgd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2225,7 +2225,9 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * takes row -1 from K2aLaneLL::fit_top instead of zeros, and the score leaves the bias behind.
  * FIT with REV (k2a_sg_rev_kernel): the start pass of ksw2amd_sg_align_batch.  Half h runs rows target[te_h - i] and
  * the whole reversed query, whatever the sign of its score; beg[tk.res[h]] = score of the pass, 0, te_h - (best row), the best row being -1
- * for the empty interval. */
+ * for the empty interval.
+ * FIT with DUAL (k2a_sgd_kernel / k2a_sgd_rev_kernel): the same two passes under the two-piece gap cost -- DUAL's chain
+ * and 16-byte boundary, FIT's bias and boundary values taken under cost(); lane 0 of the first generation gets E2' of row 0 from fit_top too. */
 template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
@@ -2283,7 +2285,8 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 			if (lane == 0 && from_bnd) {
 				if (DUAL) { const uint4 v = bnd2[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; e2 = v.z; }
 				else { const uint2 v = bnd[k2a_min(k, ncols - 1)]; h = v.x; e = v.y; }
-			} else if (FIT && lane == 0) L.fit_top(k2a_min(k, ncols - 1), h, e);
+			} else if (FIT && DUAL && lane == 0) L.fit_top(k2a_min(k, ncols - 1), h, e, e2);
+			else if (FIT && lane == 0) L.fit_top(k2a_min(k, ncols - 1), h, e);
 		};
 		uint32_t unused2 = 0;
 #pragma unroll
@@ -2373,6 +2376,24 @@ k2a_sg_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntas
                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	k2a_ll_task<PK, LDSP, true, false, false, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+/* semi-global alignment under the two-piece gap cost (ksw2amd_sgd_batch / ksw2amd_sgd_align_batch): the forward pass
+ * and the anchored start pass.  Without row maxima the packed register-profile form fits its registers (K2A_SGD_PK_REG) */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_sgd_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+               uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false, false, true, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_sgd_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true, false, true, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
 /* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
@@ -2949,6 +2970,42 @@ int k2a_shim_launch_sg_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *t
 	else if (pk) hipLaunchKernelGGL((k2a_sg_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else if (lds) hipLaunchKernelGGL((k2a_sg_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else hipLaunchKernelGGL((k2a_sg_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* semi-global alignment under the two-piece gap cost: the grids of k2a_shim_launch_sg / _rev.  K2A_SGD_PK_REG (ksw2_types.h) says whether
+ * the packed register-profile form exists; without it packed tasks take the LDS profile whatever `lds` says */
+int k2a_shim_launch_sgd(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "semi-global alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && (lds || !K2A_SGD_PK_REG)) hipLaunchKernelGGL((k2a_sgd_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+#if K2A_SGD_PK_REG
+	else if (pk) hipLaunchKernelGGL((k2a_sgd_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+#endif
+	else if (lds) hipLaunchKernelGGL((k2a_sgd_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_sgd_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+int k2a_shim_launch_sgd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "semi-global alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && (lds || !K2A_SGD_PK_REG)) hipLaunchKernelGGL((k2a_sgd_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+#if K2A_SGD_PK_REG
+	else if (pk) hipLaunchKernelGGL((k2a_sgd_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+#endif
+	else if (lds) hipLaunchKernelGGL((k2a_sgd_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_sgd_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -211,6 +211,9 @@ typedef struct K2aLL {
 /* two-piece kernels (DUAL): 1 when the packed register-profile form is built.  It is not: with f2[], the e2 chain and the 16-byte boundary
  * prefetch it needs more than 256 VGPRs and spills, so packed two-piece tasks always take the LDS profile */
 #define K2A_LLD_PK_REG 0
+/* the semi-global two-piece kernels (FIT with DUAL): 1 when the packed register-profile form is built.  It is:
+ * without rmax[] / rcol[] every one of the eight forms builds without scratch.  0 would send packed tasks to the LDS profile as above */
+#define K2A_SGD_PK_REG 1
 typedef struct K2aLLTask {
 	uint32_t roff[2], coff[2];       /* arena byte offsets of the row / column codes, per half (int32 tasks: [0]) */
 	uint32_t res[2];                 /* result slots of the halves; res[1] == res[0]: one alignment in both halves */

@@ -62,7 +62,16 @@ and of k2a_sg_kernel, their ratio and the batch-to-batch spread of k2a_ll_kernel
 --sg-align: ksw2amd_sg_align_batch on the pair array of --sg: ksw2amd_sg_batch, ksw2amd_sg_align_batch with
 KSW_EZ_SCORE_ONLY, ksw2amd_sg_align_batch with CIGARs, and the by-hand pattern they replace (sg_batch, host reversal, ksw2amd_extz_batch for
 mqe_t, ksw2amd_extz_batch for the CIGAR) alternate batch by batch, a warm-up plus --reps batches each, library calls only in the clock (the
-by-hand pattern's host work is reported beside it).  --ktrace: per batch the time of k2a_sg_kernel and of k2a_sg_rev_kernel."""
+by-hand pattern's host work is reported beside it).  --ktrace: per batch the time of k2a_sg_kernel and of k2a_sg_rev_kernel.
+
+  python tools/scripts/ll_bench.py --workload A --sgd [--ktrace kernel_trace.csv] [--out profiles/sgd_bench_A.json]
+  python tools/scripts/ll_bench.py --workload A --sgd-align [--ktrace kernel_trace.csv] [--out profiles/sgda_bench_A.json]
+
+--sgd: ksw2amd_sgd_batch under (4, 2, 24, 1) beside ksw2amd_lld_batch under the same costs and ksw2amd_sg_batch
+under (4, 2), on the pair array of --sg, the three ALTERNATING batch by batch in one process, library calls only in the clock; a parity
+sample against tests/sgd_oracle.c.  --sgd-align: ksw2amd_lld_batch, ksw2amd_sgd_align_batch with KSW_EZ_SCORE_ONLY and with CIGARs, the same
+way.  --ktrace: per batch the time of k2a_lld_kernel, k2a_sg_kernel, k2a_sgd_kernel and k2a_sgd_rev_kernel, the ratios sgd / lld and
+sgd_rev / sgd, and the batch-to-batch spread of k2a_lld_kernel."""
 import argparse
 import ctypes
 import csv
@@ -485,6 +494,92 @@ def main_sg_align(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["parity_ok"] and rec["by_hand_agrees"] else 1
 
 
+def main_sgd(a, lib, q, t, mat, gapo, gape, cells, form):
+    """--sgd / --sgd-align: the two-piece semi-global entries beside ksw2amd_lld_batch (and ksw2amd_sg_batch), alternating"""
+    from tests import sgd_util as sd
+    swap = [len(x) > len(y) for x, y in zip(q, t)]
+    q, t = [y if w else x for x, y, w in zip(q, t, swap)], [x if w else y for x, y, w in zip(q, t, swap)]      # target >= query, as --sg
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    mpp = mp.ctypes.data_as(i8p)
+    gapo2, gape2 = 24, 1
+    costs = (gapo, gape, gapo2, gape2)
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res = {k: np.zeros((n, 3), dtype=np.int32) for k in ("lld_batch", "sg_batch", "sgd_batch")}
+    alns = {k: (ksw2_amd.LocalAln * n)() for k in ("sgda_coords", "sgda_cigar")} if a.sgd_align else {}
+    rp = lambda x: x.ctypes.data_as(ctypes.POINTER(ksw2_amd.LocalResult))
+    fns = dict(lld_batch=lambda: L.ksw2amd_lld_batch(5, mpp, gapo, gape, gapo2, gape2, n, pairs, rp(res["lld_batch"])))
+    tags = dict(lld_batch="lld: pairs")
+    if a.sgd_align:
+        fns.update(sgda_coords=lambda: L.ksw2amd_sgd_align_batch(None, 5, mpp, gapo, gape, gapo2, gape2, SCORE_ONLY, n, pairs, alns["sgda_coords"]),
+                   sgda_cigar=lambda: L.ksw2amd_sgd_align_batch(None, 5, mpp, gapo, gape, gapo2, gape2, 0, n, pairs, alns["sgda_cigar"]))
+        tags.update(sgda_coords="sgda: pairs", sgda_cigar="sgda: pairs")
+    else:
+        fns.update(sg_batch=lambda: L.ksw2amd_sg_batch(5, mpp, gapo, gape, n, pairs, rp(res["sg_batch"])),
+                   sgd_batch=lambda: L.ksw2amd_sgd_batch(5, mpp, gapo, gape, gapo2, gape2, n, pairs, rp(res["sgd_batch"])))
+        tags.update(sg_batch="sg: pairs", sgd_batch="sgd: pairs")
+    forms = {}
+    os.environ["KSW2AMD_TRACE"] = "1"                          # the warm-ups' form lines
+    for name, fn in fns.items():
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            forms[name] = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tags[name] in l]
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+    os.environ.pop("KSW2AMD_TRACE")                            # (the binding re-reads the environment in front of every call)
+    times = {name: [] for name in fns}
+    for _ in range(a.reps):                                    # alternating batch by batch
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    rec = dict(workload=a.workload, mode="sgd-align" if a.sgd_align else "sgd", pairs=n, cells=cells, ll_form=form, costs=list(costs),
+               pairs_turned_round=int(sum(swap)), clock="library call only: the pair array is built before it; the entries alternate batch by batch")
+    for name in fns:
+        ts = times[name]
+        rec[name] = dict(e2e_s=min(ts), e2e_all_s=ts, pairs_per_s=n / min(ts), e2e_gcups=cells / min(ts) / 1e9, forms=forms[name])
+    rec["lld_e2e_spread"] = (max(times["lld_batch"]) - min(times["lld_batch"])) / min(times["lld_batch"])
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = sd.oracle_cells([q[i] for i in idx], [t[i] for i in idx], mat, costs, 5)
+    rec["parity_sample"] = int(len(idx))
+    if a.sgd_align:
+        got = [[[x.score, x.qb, x.qe, x.tb, x.te] for x in (alns[k][int(i)] for i in idx)] for k in ("sgda_coords", "sgda_cigar")]
+        rec["parity_ok"] = bool(got[0] == exp.tolist() and got[1] == exp.tolist())
+        rec["empty_intervals"] = int(sum(x.tb > x.te for x in alns["sgda_coords"]))
+    else:
+        rec["parity_ok"] = bool((res["sgd_batch"][idx] == exp[:, [0, 2, 4]]).all())
+        rec["scores_differing_from_sg"] = int((res["sgd_batch"][:, 0] != res["sg_batch"][:, 0]).sum())
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        first = "sgda_coords" if a.sgd_align else "sgd_batch"
+        kl = trace_batches(a.ktrace, "k2a_lld_kernel", nl(forms["lld_batch"][0]))[1:]        # [0]: the warm-up
+        kd = trace_batches(a.ktrace, "k2a_sgd_kernel", nl(forms[first][0]))
+        kr = trace_batches(a.ktrace, "k2a_sgd_rev_kernel", nl(forms[first][0]))
+        kd, kr = kd[(2 if a.sgd_align else 1):], kr[2:]       # the warm-ups: one per entry that launches the kernel
+        ks = trace_batches(a.ktrace, "k2a_sg_kernel", nl(forms["sg_batch"][0]))[1:] if not a.sgd_align else []
+        mean = lambda x: sum(x) / len(x) if x else None
+        rec["kernel"] = dict(lld_kernel_ms=kl, sg_kernel_ms=ks, sgd_kernel_ms=kd, sgd_rev_kernel_ms=kr,
+                             lld_kernel_spread=(max(kl) - min(kl)) / min(kl) if kl else None,
+                             sgd_over_lld=mean(kd) / mean(kl) if kl and kd else None,
+                             sgd_over_sg=mean(kd) / mean(ks) if ks and kd else None,
+                             sgd_rev_over_sgd=mean(kr) / mean(kd) if kr and kd else None)
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] else 1
+
+
 def main_dual(a, lib, q, t, mat, gapo, gape, cells, form):
     from tests import lld_util as ld
     n = len(q)
@@ -656,6 +751,8 @@ def main():
     ap.add_argument("--dual", action="store_true", help="ksw2amd_lld_batch under (4, 2, 24, 1) beside ksw2amd_ll_batch under (4, 2); with --align the align entries; with --sub ksw2amd_lld_sub_batch beside ksw2amd_lld_batch")
     ap.add_argument("--sg", action="store_true", help="ksw2amd_sg_batch beside ksw2amd_ll_batch on the same pair array (target >= query), alternating, library calls only in the clock")
     ap.add_argument("--sg-align", action="store_true", help="ksw2amd_sg_batch, ksw2amd_sg_align_batch (SCORE_ONLY and with CIGARs) and the by-hand pattern (sg_batch, host reversal, two ksw2amd_extz_batch calls) on the same pair array, alternating")
+    ap.add_argument("--sgd", action="store_true", help="ksw2amd_sgd_batch under (4, 2, 24, 1) beside ksw2amd_lld_batch and ksw2amd_sg_batch on the pair array of --sg, alternating, library calls only in the clock")
+    ap.add_argument("--sgd-align", action="store_true", help="ksw2amd_lld_batch and ksw2amd_sgd_align_batch (SCORE_ONLY and with CIGARs) on the same pair array, alternating")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -672,6 +769,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.sgd or a.sgd_align:
+        return main_sgd(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sg_align:
         return main_sg_align(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sg:
