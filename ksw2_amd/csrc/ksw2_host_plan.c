@@ -1150,7 +1150,7 @@ ksw2amd_plan_t *plan_create_ex(int dual, int scalar, const ksw2amd_scoring_t *sc
 						steps = (uint32_t)imax((int)steps, (int)ns - 1 + imin(d->qlen - 1, d->tlen - 1 + d->w) + 1);
 						hs = (uint32_t)imax((int)hs, (int)ns);
 					}
-					bytes = align_up((size_t)steps * 512 + (size_t)NG * hs * 16, 256);
+					bytes = align_up(K2A_CK_BLOCK_BYTES(steps, NG, hs, C), 256);
 					if (lo) for (t = t0; t < imin(c->count, t0 + NG); ++t) {
 						K2aPair *da = &p->h_pairs[p->h_order[c->first + 2 * t]], *db = &p->h_pairs[p->h_order[c->first + 2 * t + 1]];
 						da->tb_off = db->tb_off = at; da->bnd_off = db->bnd_off = steps; da->cig_off = db->cig_off = hs;
@@ -1443,7 +1443,7 @@ static ksw2amd_plan_t *plan_create_uniform(int dual, int scalar, const ksw2amd_s
 	p->ncls = 1; p->cls[0] = c0; p->cls[0].first = 0; p->cls[0].count = n / 2; p->cls[0].qd = 0; p->ntasks = n / 2; p->norder = n;
 	if (c0.defer) {                                              /* checkpoint blocks, one per wavefront-task (plan_create_ex, "Deferred arg-max") */
 		const uint32_t ns = (uint32_t)((tm.tlen + C - 1) / C), steps = ns - 1 + (uint32_t)imin(tm.qlen - 1, tm.tlen - 1 + tm.w) + 1;
-		const size_t bytes = align_up((size_t)steps * 512 + (size_t)NG * ns * 16, 256), zl = align_up(4 * K2A_ZLIST_WORDS(n / 2), 256);
+		const size_t bytes = align_up(K2A_CK_BLOCK_BYTES(steps, NG, ns, C), 256), zl = align_up(4 * K2A_ZLIST_WORDS(n / 2), 256);
 		size_t free_b = 0, total_b = 0;
 		if (zl + (size_t)nwt * bytes > ((size_t)1 << 30) && !(ENV(DEFER) && *ENV(DEFER)) &&
 		    (k2a_shim_mem_info(&free_b, &total_b) || zl + (size_t)nwt * bytes > (free_b + thread_cached_device_bytes()) / 10 * 6)) { g_err[0] = 0; goto na; }   /* (the general path decides what then) */

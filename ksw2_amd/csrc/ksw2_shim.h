@@ -93,7 +93,9 @@ int k2a_shim_launch_trace(int cfg, int dual, const K2aPair *pairs, const uint32_
  * lane's top inputs into `tb`; a second kernel of the same launch call re-runs the strips whose columns the results need
  * (K2aLanePk, DEFER).  Every pair of a wavefront carries the wavefront's checkpoint block in tb_off (byte offset in tb), its
  * stream length in steps in bnd_off and the strips-per-group stride of its header table in cig_off:
- *   block = [bnd_off steps][64 lanes] x 8 bytes, then [64 / G groups][cig_off strips] x 16 bytes (K2aCkHead). */
+ *   block = [bnd_off steps][64 lanes] x 8 bytes, then [64 / G groups][cig_off strips] x 16 bytes (K2aCkHead), then -- G = 64 only,
+ *   K2A_FOLD_AFTER -- [cig_off strips] x K2A_CK_REC_WORDS(C) dwords: the strips' records { rmax[C], hl[C] } that the fill folds into
+ *   the books behind its step loop (ksw2_lane_pkfold.h).  K2A_CK_BLOCK_BYTES (ksw2_types.h) is the block's size. */
 /* qd != NULL (device pointer, K2aQueueDesc in ksw2_types.h): a streamed launch -- the ordinary full grid, every wavefront's task given
  * by its position in the grid, started under the upload: a wavefront first waits (k2a_queue_wait) until the watermark says that the
  * qd->need[] pieces its task lies in have landed, or gives up after the timeout and sets qd->abort; qd->next only counts the

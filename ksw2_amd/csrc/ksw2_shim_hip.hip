@@ -13,6 +13,7 @@
 #include "ksw2_shim.h"
 #include "ksw2_lane.h"
 #include "ksw2_lane_pk.h"
+#include "ksw2_lane_pkfold.h"
 #include "ksw2_lane_pkmp.h"
 #include "ksw2_lane_solo.h"
 #include "ksw2_lane_dm.h"
@@ -403,6 +404,9 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	 * the inner loop.  An all-invalid wavefront: klast = kmax = -1 and the loop is never entered.  So the test is compiled out
 	 * there: two v_readlane, a select, a compare and the scalar registers of klast and gdone per step. */
 	constexpr bool NOSTOP = K2A_STEP_TRIM != 0 && DEFER && NG == 1;
+	/* ... and nothing inside the loop reads the books there, so the strip ends are folded into them once, behind the loop
+	 * (ksw2_lane_pkfold.h): the lane whose strip ends stores the strip's record and is done */
+	constexpr bool FOLD = K2A_FOLD_AFTER != 0 && DEFER && NG == 1 && !NOMAX && MODE == K2A_MODE_SCORE;
 	K2aRowMasks<C> RM;
 	RM.reset();
 	Stage ST;
@@ -416,6 +420,8 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	uint2 *ckst = (uint2*)(tb + ckoff) + lane;
 	K2aCkHead *ckhd = (K2aCkHead*)(tb + ckoff + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)prA.bnd_off) * K2A_CK_STEP_BYTES) +
 	                  (size_t)grp * (uint32_t)__builtin_amdgcn_readfirstlane((int)prA.cig_off);
+	/* FOLD: the strips' records lie behind the header table (K2A_CK_BLOCK_BYTES, ksw2_types.h) */
+	uint32_t *ckrec = (uint32_t*)(ckhd + (FOLD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)prA.cig_off) : 0u));
 
 	/* Steps in groups of four: the query dwords of the NEXT group are asked for at the top of a group and taken over below its
 	 * last step, four steps in flight (K2aLanePk::load_query_group).  The inner loop stays rolled. */
@@ -483,7 +489,21 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 		if (finmask != 0) {
 			if (UMASK) RM.on_fin(finmask);                      /* end_strip(): every row of these lanes is dead from the next step on */
 			uint32_t *rowbuf = &stage_w[grp * K2A_PK_STAGE(C)];
-			if (NOMAX) {
+			if (FOLD) {
+				/* the record: the row maxima, and the last H column where a row of the strip reaches the query end -- the only rows
+				 * whose H the fold reads (mqe, score: k2a_pkfold_strip_reaches; 31 of the headline's 625 strips), so the other
+				 * strips save half the stores */
+				if (nfin) {
+					uint4 *r4 = (uint4*)(ckrec + (size_t)L.S * K2A_CK_REC_WORDS(C));
+#pragma unroll
+					for (int c = 0; c < C; c += 4) r4[c / 4] = make_uint4(L.rmax(c), L.rmax(c + 1), L.rmax(c + 2), L.rmax(c + 3));
+					if (k2a_pkfold_strip_reaches<C>(L.S, L.qlen, L.tlen, L.w)) {
+#pragma unroll
+						for (int c = 0; c < C; c += 4) r4[(C + c) / 4] = make_uint4(L.hl[c], L.hl[c + 1], L.hl[c + 2], L.hl[c + 3]);
+					}
+					L.end_strip();
+				}
+			} else if (NOMAX) {
 				if (nfin) L.fin_score_only(sc, bkA, bkB);
 			} else if (zseq) {
 				/* most strips fold into the books from registers; the rest take the row-by-row scan */
@@ -510,7 +530,14 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	}
 	if (STAGED) ST.finish(kdone);
 	__builtin_amdgcn_wave_barrier();
-	if (!zseq) {
+	if (FOLD) {
+		/* the records were stored by lanes of this wavefront and are read by others of it: the stores drained and one fence at the
+		 * narrowest scope that orders them within a CU, once per task */
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		if (ckon) k2a_pkfold_task<C, 1>(sc, ckrec, ckhd, L.nstrips, L.qlen, L.tlen, L.tlen_full, L.w, zdropA, zdropB, bkA, bkB, stage_w, lane);
+		__builtin_amdgcn_wave_barrier();
+	} else if (!zseq) {
 		/* merge the lane-local bests of each group; the lane that finished the last target row adds mte / score */
 		uint32_t *loc = &stage_w[0];
 		loc[lane * 5 + 0] = L.lmax; loc[lane * 5 + 1] = L.lmax_t; loc[lane * 5 + 2] = L.lmax_q;
@@ -550,6 +577,7 @@ k2a_fill_pk_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const
 	typedef K2aLanePk<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, false> Lane;      /* (sizes only: both builds of the body have the same) */
 	__shared__ K2aBook book[K2A_WPB][NG][2];
 	__shared__ uint32_t stage[K2A_WPB][(NG * K2A_PK_STAGE(C) > 64 * 5) ? NG * K2A_PK_STAGE(C) : 64 * 5];   /* row buffers / final lane records */
+	static_assert(64 * 5 >= K2A_PKFOLD_XB_WORDS, "the fold's exchange buffer is the stage");
 
 	const int lane = threadIdx.x & 63, wave = k2a_wave_id<(C <= 8 || LDSROW || (NOMAX && DUAL && MODE != K2A_MODE_SCORE))>();   /* 16 rows, two-piece, traceback: part of what gets those kernels to two wavefronts */
 	const int grp = lane / G, gl = lane % G;

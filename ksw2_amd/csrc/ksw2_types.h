@@ -52,6 +52,17 @@
 #ifndef K2A_HL_OPEN
 #define K2A_HL_OPEN 1
 #endif
+/* where the deferred fills of one group per wavefront (G = 64) fold their strip ends into the books (ksw2_lane_pkfold.h): 1 = once per
+ * task behind the step loop, from one record per strip in the checkpoint block; 0 = at the step a strip ends, the form before (A/B
+ * libraries).  Here, because the host sizes the blocks.
+ * A wavefront's checkpoint block: the stream of `steps` x 64 lanes x 8 bytes, the K2aCkHead table of NG groups x hs strips, and -- NG = 1
+ * only -- hs records of K2A_CK_REC_WORDS(C) dwords (a strip's rmax[C] and hl[C]); the stream and the headers lie where they lay. */
+#ifndef K2A_FOLD_AFTER
+#define K2A_FOLD_AFTER 1
+#endif
+#define K2A_CK_REC_WORDS(C) (2 * (C))
+#define K2A_CK_BLOCK_BYTES(steps, NG, hs, C) \
+	((size_t)(steps) * 512 + (size_t)(NG) * (hs) * 16 + ((K2A_FOLD_AFTER) && (NG) == 1 ? (size_t)(hs) * K2A_CK_REC_WORDS(C) * 4 : (size_t)0))
 #define K2A_PK_NIBBLES(C, dual) (!(dual) && (C) == 16)
 #define K2A_PK_TB_BYTES(C, dual) (K2A_PK_NIBBLES(C, dual) ? (C) : 2 * (C))        /* per lane-step: C rows x 2 alignments */
 
