@@ -430,8 +430,8 @@ int ksw2amd_lld_sub(void *q, int tlen, const uint8_t *target, int gapo, int gape
  * without a positive entry is legal here (the local entries skip such pairs; these do not).  Every argument and every code is checked
  * before anything is staged or launched (KSW2AMD_E_PARAM); the flat entry checks the codes on the device, chunk by chunk, and has the
  * chunking, reset and error semantics and the on_device behaviour of ksw2amd_ll_batch_flat.
- * Not computed: free query ends, a suboptimal score (the start tb and a CIGAR: ksw2amd_sg_align_batch below; the two-piece gap cost:
- * ksw2amd_sgd_batch further below).
+ * Free query ends (overlap alignment): ksw2amd_ov_batch further below.  Not computed: a suboptimal score (the start tb and a CIGAR:
+ * ksw2amd_sg_align_batch below; the two-piece gap cost: ksw2amd_sgd_batch further below).
  * ksw2amd_sg: one pair on a ksw_ll_qinit profile; returns the score, equal to row 0 of ksw2amd_sg_batch on that pair.  On a device
  * failure or a bad argument it returns 0 with *qe = *te = -1 and reports like ksw_ll_i16 (ksw2amd_error_count, ksw2amd_last_error, the
  * handler, KSW2AMD_ABORT_ON_ERROR). */
@@ -464,7 +464,8 @@ int ksw2amd_sg(void *q, int tlen, const uint8_t *target, int gapo, int gape, int
  * intervals come back once for the CIGAR stage; on a failure every aln[] entry holds score 0, coordinates -1, n_cigar 0).
  * ksw2amd_sg_align: one pair on a ksw_ll_qinit profile; returns the score; on a failure 0 with those reset values, reported like
  * ksw_ll_i16.  Device failures: a negative code, no CPU fallback.
- * Not computed, here either: free query ends, a suboptimal score (the two-piece gap cost: ksw2amd_sgd_align_batch below). */
+ * Free query ends: ksw2amd_ov_batch further below, score and end cell only -- the start cell and CIGAR of that mode are not computed yet,
+ * nor is a suboptimal score (the two-piece gap cost: ksw2amd_sgd_align_batch below). */
 int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
                            const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
 int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
@@ -495,13 +496,44 @@ int ksw2amd_sg_align(void *km, void *q, int tlen, const uint8_t *target, int gap
  * Everything else is as for the ksw2amd_sg_* entries: every argument checked before anything is staged or launched, flat chunking, the
  * on-device code check, the reset values on a failure, on_device arenas, no CPU fallback, KSW2AMD_LL_FORM / KSW2AMD_LL_LDS /
  * KSW2AMD_LL_CHUNK_BYTES; the single-pair entries report failures like ksw_ll_i16.
- * Not computed: free query ends, a suboptimal score. */
+ * Free query ends: ksw2amd_ovd_batch below.  Not computed: a suboptimal score. */
 int ksw2amd_sgd_batch(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 int ksw2amd_sgd_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res);
 int ksw2amd_sgd(void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int *qe, int *te);
 int ksw2amd_sgd_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
 int ksw2amd_sgd_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln);
 int ksw2amd_sgd_align(void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int flag, ksw2amd_laln_t *aln);
+
+/* Overlap alignment (new): ksw2amd_sg_batch / ksw2amd_sgd_batch with the query's ends free as `ends`
+ * says.  Both bits: overlap (dovetail) alignment, the suffix of one sequence against the prefix of the other, or one contained in the
+ * other; one bit: the query may hang over the left (QBEG) or the right (QEND) end of the target, as adapter trimming and clipping at a
+ * contig edge need.  The target's two ends are always free.  cost(l) = gapo + l * gape for the ov entries, min(gapo + l * gape, gapo2 + l * gape2)
+ * with the pieces as the caller orders them for the ovd entries; t the target index, j the query index, -1 the boundary:
+ *   H(t, -1) = 0 for every t >= -1;   H(-1, j) = 0 if ends & KSW2AMD_OV_QBEG, else -cost(j + 1);   the gap states are -infinity on the boundary;
+ *   the recurrence is that of ksw_extz / ksw_extd, with NO clamp at 0;
+ *   candidates: the cells (t, qlen - 1), 0 <= t < tlen, and with ends & KSW2AMD_OV_QEND the cells (tlen - 1, j), 0 <= j < qlen, as well -- real
+ *   cells only, never the boundary row or column, so the score may be slightly negative even with both bits;
+ *   result: the largest H over the candidates, then the smallest te, then the smallest qe (a tie between the last column and the last row goes
+ *   to the last column, ties inside the last row to the smaller column).
+ * ends: any other bit is KSW2AMD_E_PARAM, checked before anything is staged; ends == 0 returns ksw2amd_sg_batch's (ksw2amd_sgd_batch's) result
+ * bit for bit.  Nothing is launched for qlen <= 0 -> (0, -1, -1), nor for tlen <= 0 with qlen > 0 -> ((ends & KSW2AMD_OV_QBEG) ? 0 :
+ * -cost(qlen), qlen - 1, -1), whatever KSW2AMD_OV_QEND says.
+ * In the reference's terms: with r = ksw_extz(reverse(query[0..qe]), reverse(target[0..te]), w = -1, zdrop = -1, KSW_EZ_SCORE_ONLY) (ksw_extd
+ * for the ovd entries), the value of a cell (te, qe) is max(r.mqe, -cost(qe + 1)), and with KSW2AMD_OV_QBEG max(r.mqe, -cost(qe + 1), r.mte,
+ * -cost(te + 1)); the result is the best value over the candidates under the tie rule.
+ * Equal pieces: with (gapo2, gape2) = (gapo, gape), or with gapo2 >= gapo and gape2 >= gape, the ovd entries equal the ov entries in every field.
+ * Scoring arguments, ranges, residue codes, the 0x3fffffff rejection, flat chunking, the on-device code check, the reset values, on_device
+ * arenas and error reporting are exactly those of ksw2amd_sg_batch / ksw2amd_sgd_batch; no CPU fallback.  ksw2amd_ov / ksw2amd_ovd: one pair on
+ * a ksw_ll_qinit profile, failures reported like ksw_ll_i16.
+ * Not computed yet: the start cell and a CIGAR of this mode, a suboptimal score. */
+#define KSW2AMD_OV_QBEG 1   /* the query's start is free: a query prefix may stay unaligned at no cost */
+#define KSW2AMD_OV_QEND 2   /* the query's end is free:   a query suffix may stay unaligned at no cost */
+int ksw2amd_ov_batch      (int m, const int8_t *mat, int gapo, int gape, int ends, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
+int ksw2amd_ov_batch_flat (int m, const int8_t *mat, int gapo, int gape, int ends, int n, const ksw2amd_lflat_t *in,    ksw2amd_lres_t *res);
+int ksw2amd_ov            (void *q, int tlen, const uint8_t *target, int gapo, int gape, int ends, int *qe, int *te);
+int ksw2amd_ovd_batch     (int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
+int ksw2amd_ovd_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int n, const ksw2amd_lflat_t *in,    ksw2amd_lres_t *res);
+int ksw2amd_ovd           (void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int ends, int *qe, int *te);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

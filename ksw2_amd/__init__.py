@@ -117,7 +117,8 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
            "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
            "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
-           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align"]
+           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align",
+           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -132,7 +133,9 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
                 "ksw2amd_sg_batch", "ksw2amd_sg_batch_flat", "ksw2amd_sg",
            "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
            "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
-           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align"]
+           "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align",
+           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd"]
+KSW2AMD_OV_QBEG, KSW2AMD_OV_QEND = 1, 2      # ov_batch / ovd_batch: the query's start / end is free
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
 
@@ -303,6 +306,13 @@ class Library:
             L.ksw2amd_sgd_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
             L.ksw2amd_sgd_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
             L.ksw2amd_sgd_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalAln)]
+        if hasattr(L, "ksw2amd_ov_batch"):          # (nor the overlap entries and their launches' twin: tests/ov_util.py adds them)
+            L.ksw2amd_ov_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_ov_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_ov.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+            L.ksw2amd_ovd_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_ovd_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
+            L.ksw2amd_ovd.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -852,6 +862,70 @@ class Library:
         try:
             qe, te = _int(0), _int(0)
             score = self.lib.ksw2amd_sgd(prof, len(ta), tp, gapo, gape, gapo2, gape2, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
+
+    # ---- overlap alignment: sg_batch / sgd_batch with the query's ends free (ends: KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND)
+    def ov_batch(self, queries, targets, mat, gapo, gape, ends, m=None, pairs=None, n=None, costs2=None):
+        """ksw2amd_ov_batch (costs2 = (gapo2, gape2): ksw2amd_ovd_batch): the best score of the query against an interval of the target
+        with the query's start (ends & 1) and / or end (ends & 2) free -> (n, 3) int32 array of score, qe, te."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        out = np.zeros((max(n, 1), 3), dtype=np.int32)
+        if costs2 is None:
+            rc = self.lib.ksw2amd_ov_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, ends, n, pairs, out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        else:
+            rc = self.lib.ksw2amd_ovd_batch(m, mat.ctypes.data_as(_i8p), gapo, gape, costs2[0], costs2[1], ends, n, pairs,
+                                            out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def ovd_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, ends, m=None, pairs=None, n=None):
+        """ksw2amd_ovd_batch: ov_batch under the two-piece gap cost."""
+        return self.ov_batch(queries, targets, mat, gapo, gape, ends, m=m, pairs=pairs, n=n, costs2=(gapo2, gape2))
+
+    def ov_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, ends, m=None, device_base=None, out=None, costs2=None):
+        """ksw2amd_ov_batch_flat (costs2: ksw2amd_ovd_batch_flat): ov_batch on an arena (see ll_batch_flat) -> (n, 3) int32 array."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        out = np.zeros((max(n, 1), 3), dtype=np.int32) if out is None else out
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1] == 3
+        if costs2 is None:
+            rc = self.lib.ksw2amd_ov_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, ends, n, ctypes.byref(f),
+                                                out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        else:
+            rc = self.lib.ksw2amd_ovd_batch_flat(m, mat.ctypes.data_as(_i8p), gapo, gape, costs2[0], costs2[1], ends, n, ctypes.byref(f),
+                                                 out.ctypes.data_as(ctypes.POINTER(LocalResult)))
+        self._check(rc)
+        return out[:n]
+
+    def ovd_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, gapo2, gape2, ends, m=None, device_base=None, out=None):
+        """ksw2amd_ovd_batch_flat: ov_batch_flat under the two-piece gap cost."""
+        return self.ov_batch_flat(base, qoff, qlen, toff, tlen, mat, gapo, gape, ends, m=m, device_base=device_base, out=out, costs2=(gapo2, gape2))
+
+    def ov(self, query, target, mat, gapo, gape, ends, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_ov -> (score, qe, te)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw2amd_ov(prof, len(ta), tp, gapo, gape, ends, ctypes.byref(qe), ctypes.byref(te))
+        finally:
+            _libc.free(prof)
+        return int(score), qe.value, te.value
+
+    def ovd(self, query, target, mat, gapo, gape, gapo2, gape2, ends, m=None, size=2):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_ovd -> (score, qe, te)."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            qe, te = _int(0), _int(0)
+            score = self.lib.ksw2amd_ovd(prof, len(ta), tp, gapo, gape, gapo2, gape2, ends, ctypes.byref(qe), ctypes.byref(te))
         finally:
             _libc.free(prof)
         return int(score), qe.value, te.value

@@ -330,15 +330,21 @@ typedef struct {
  * skipped, and a matrix without a positive entry still launches.  With a rev as well (ksw2_host_sga.c): rev is
  * k2a_shim_launch_sg_rev, the anchored start pass, which only ksw2_host_sga.o names.  With an ll_dual_t as well (ksw2_host_sgd.c, DESIGN.md
  * section 3.22): launch = k2a_shim_launch_sgd and rev = k2a_shim_launch_sgd_rev, which only ksw2_host_sgd.o names; the ll_dual_t's fwd is not
- * called and may be NULL */
+ * called and may be NULL.
+ * ov (ksw2_host_ov.c): the overlap entries -- launch = k2a_shim_launch_ov (with an ll_dual_t: k2a_shim_launch_ovd), which
+ * only ksw2_host_ov.o names; never with a rev.  ends (KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND, checked by ll_batch_ex / llf_batch_ex) travels to the
+ * kernels in every task's pad, a pair with the query's end free is packed only if its columns fit the 16-bit index as well, a query without a
+ * target scores 0 when its start is free, and the trace line says "ov" (two-piece: "ovd") and ends.  Every other entry sets ov = ends = 0 */
 typedef struct {
 	ll_fwd_fn launch;
+	int ov, ends;
 } ll_fit_t;
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft);
 size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit);
 int ll_sg_pk_admit(int qlen, int gapo, int gape, const ll_dual_t *du, int smax);      /* du: cost(qlen) of the two pieces */
 int ll_sg_check_range(int i, int qlen, int gapo, int gape, const ll_dual_t *du, int smax);
+int ll_ov_check_ends(const ll_fit_t *ft);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,

@@ -51,6 +51,13 @@ int ll_sg_check_range(int i, int qlen, int gapo, int gape, const ll_dual_t *du, 
 	return fail(KSW2AMD_E_PARAM, "semi-global alignment: pair %s: gapo + qlen * (gape + smax) + smax exceeds 0x3fffffff", msg);
 }
 
+/* the overlap entries' `ends`: the two bits and nothing else, before anything is staged */
+int ll_ov_check_ends(const ll_fit_t *ft)
+{
+	if (ft && ft->ov && (ft->ends & ~(KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND))) return fail(KSW2AMD_E_PARAM, "overlap alignment: ends must be a combination of KSW2AMD_OV_QBEG and KSW2AMD_OV_QEND%s", "");
+	return KSW2AMD_OK;
+}
+
 /* a pair's share of a chunk's byte budget: sequences, table entries, results, the generation boundary (8 bytes per column of a task
  * over one generation; dual: 16) and -- sub: rows = target whatever the lengths -- the row profile; fit: rows = target, no profile */
 size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit)
@@ -120,14 +127,15 @@ static int ll_check_list(const ll_src_t *src, int n, K2aLLChk *ent)
 	return nent;
 }
 
-/* semi-global mode: the pairs of a chunk that launch nothing and still have a result -- a query without a target */
-static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const ll_dual_t *du, ksw2amd_lres_t *res, K2aLLBeg *beg)
+/* semi-global mode: the pairs of a chunk that launch nothing and still have a result -- a query without a target; free_beg (the overlap
+ * entries with the query's start free): nothing of it has to be inserted */
+static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const ll_dual_t *du, int free_beg, ksw2amd_lres_t *res, K2aLLBeg *beg)
 {
 	int i;
 	for (i = 0; i < n; ++i) {
 		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
 		if (ql > 0 && tl <= 0) {                                 /* the whole query inserted before the target */
-			res[i].score = -(int)ll_sg_cost(ql, gapo, gape, du); res[i].qe = ql - 1; res[i].te = -1;
+			res[i].score = free_beg ? 0 : -(int)ll_sg_cost(ql, gapo, gape, du); res[i].qe = ql - 1; res[i].te = -1;
 			if (beg) { beg[i].score = res[i].score; beg[i].qb = 0; beg[i].tb = 0; }      /* (rev: the empty interval, tb = te + 1) */
 		}
 	}
@@ -154,7 +162,10 @@ static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const
  * score, 0, tb (te + 1 for the empty interval), a corner pair's filled in with its result; the trace lines say "sga"
  * ft and du together (never with sb): ksw2amd_sgd_batch and, with rev, ksw2amd_sgd_align_batch (ksw2_host_sgd.c) --
  * the forward launch is ft->launch (du->fwd is not called), par.oe2 / ge2 and the 16-byte boundary come from du, the corners, the packed
- * admission and the range check use cost(qlen) = min of the two pieces; the trace lines say "sgd" / "sgda" */
+ * admission and the range check use cost(qlen) = min of the two pieces; the trace lines say "sgd" / "sgda"
+ * ft->ov (never with rev or sb; with and without du): ksw2amd_ov_batch / ksw2amd_ovd_batch (ksw2_host_ov.c) -- the
+ * semi-global chunk with ft->ends in every task's pad; a pair whose query end is free is packed only if qlen - 1 fits the packed form's
+ * 16-bit column index as well, a query without a target scores 0 if its start is free; the trace line says "ov" / "ovd" and ends */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft)
 {
@@ -162,7 +173,9 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
 	const ll_fwd_fn fwd = ft ? ft->launch : du ? du->fwd : k2a_shim_launch_ll;
-	const char *tn = ft ? (du ? (rev ? "sgda" : "sgd") : rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
+	const char *tn = ft && ft->ov ? (du ? "ovd" : "ov") : ft ? (du ? (rev ? "sgda" : "sgd") : rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
+	const int ov_end = ft && ft->ov && (ft->ends & KSW2AMD_OV_QEND);
+	char ovs[24] = "";
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));
 	K2aLLTask *tk = 0;
@@ -185,7 +198,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		s.rows = imax(ql, tl); s.cols = imin(ql, tl); s.sw = ql > tl; s.idx = (uint32_t)i;
 		if (sb || ft) { s.rows = tl; s.cols = ql; s.sw = 0; }    /* row maxima (ft: the last column) are per target position only if rows = target */
 		s.cost = (int64_t)((s.rows + K2A_LL_ROWS - 1) / K2A_LL_ROWS) * (s.cols + 63);
-		if (form > 0 && (ft ? ll_sg_pk_admit(ql, gapo, gape, du, smax) : ll_pk_admit(ql, tl, smax) && s.cols <= 65535)) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
+		if (form > 0 && (ft ? ll_sg_pk_admit(ql, gapo, gape, du, smax) && (!ov_end || ql - 1 <= 65535) : ll_pk_admit(ql, tl, smax) && s.cols <= 65535)) pk[npk++] = s;      /* (sb: the query fits the 16-bit column index) */
 		else i32[ni32++] = s;
 	}
 	/* packed tasks: equal shapes (rows, columns, orientation) side by side; with form 1 a pair without a partner of its shape goes to the int32 form */
@@ -205,13 +218,14 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	qsort(pk, (size_t)ntk_pk, 2 * sizeof(ll_sort_t), cmp_cost);        /* tasks (pairs of entries) longest first */
 	qsort(i32, (size_t)ni32, sizeof(ll_sort_t), cmp_cost);
 	ntk = ntk_pk + ni32;
-	if (trace_on()) fprintf(stderr, "[ksw2_amd] %s: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s%s\n", tn, n, ntk_pk, ni32, lds ? "lds" : "registers",
+	if (ft && ft->ov) snprintf(ovs, sizeof(ovs), " ends=%d", ft->ends);
+	if (trace_on()) fprintf(stderr, "[ksw2_amd] %s: pairs=%d pk_tasks=%d int32_tasks=%d profile=%s%s%s%s\n", tn, n, ntk_pk, ni32, lds ? "lds" : "registers", ovs,
 	                        !flat ? "" : flat->on_device ? " arena=device" : " arena=host", du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (rev && trace_on()) fprintf(stderr, "[ksw2_amd] %s-rev: pk_tasks=%d int32_tasks=%d profile=%s%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers",
 	                               du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
 	if (sb && trace_on()) fprintf(stderr, "[ksw2_amd] %s-sub: pk_tasks=%d int32_tasks=%d profile=%s excl=%d%s\n", tn, ntk_pk, ni32, lds ? "lds" : "registers", sb->excl,
 	                              du && !lds && !du->pk_reg ? " pk_profile=lds" : "");
-	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, du, res, rev ? beg : 0); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
+	if (ntk == 0 && !flat) { if (ft) ll_fit_corners(src, n, gapo, gape, du, ft->ov && (ft->ends & KSW2AMD_OV_QBEG), res, rev ? beg : 0); free(pk); free(i32); return KSW2AMD_OK; }         /* a borrowed chunk without tasks still has its codes checked */
 	/* gathered: task table | pen tables (rows = target, rows = query) | sequences (rows, then columns, of every pair once)
 	 * borrowed: task table | pen tables | check list (2 n + 1 entries at most) | result word of the check */
 	tab_off = align_up(sizeof(K2aLLTask) * (size_t)ntk, 256);
@@ -267,6 +281,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 			}
 			if (!is_pk) { k->res[1] = k->res[0]; k->roff[1] = k->roff[0]; k->coff[1] = k->coff[0]; }
 			if (k->nrows > K2A_LL_ROWS) { k->boff = scr; scr += align_up((size_t)k->ncols * (du ? 16 : 8), 256); }
+			if (ft && ft->ov) k->pad = ft->ends;
 			if (sb) { k->pad = (int32_t)(prof / 128); prof += align_up(K2A_LLSUB_BYTES(k->nrows), 256); }
 		}
 	}
@@ -325,7 +340,7 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 		for (i = 0; i < ni32; ++i) memcpy(&sub[i32[i].idx], &hs[i32[i].idx], sizeof(K2aLLSub));
 	}
 done:
-	if (ft) ll_fit_corners(src, n, gapo, gape, du, res, rev ? beg : 0);
+	if (ft) ll_fit_corners(src, n, gapo, gape, du, ft->ov && (ft->ends & KSW2AMD_OV_QBEG), res, rev ? beg : 0);
 out:
 	if (d_scr) cache_put(BUF_TB, d_scr, cap_s);
 	if (d_span) cache_put(BUF_SEQ, d_span, cap_sp);
@@ -345,6 +360,7 @@ int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2a
 	int i, rc, beg = 0, smax = -128, any = 0;
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || (n > 0 && (!pairs || !res || (rev && !begs) || (sb && !subs)))) return fail(KSW2AMD_E_PARAM, "local alignment: bad pair array%s", "");
+	if ((rc = ll_ov_check_ends(ft)) != KSW2AMD_OK) return rc;
 	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
 	if (ft) smax = imax(smax, 0);
 	for (i = 0; i < n; ++i) {                              /* every argument before anything runs */

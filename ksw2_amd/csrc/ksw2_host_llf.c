@@ -40,6 +40,7 @@ int llf_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2
 	if ((rc = ll_check_args(m, mat, gapo, gape)) != KSW2AMD_OK || (du && (rc = ll_check_args(m, mat, du->gapo2, du->gape2)) != KSW2AMD_OK)) return rc;
 	if (n < 0 || !in || (n > 0 && (!in->base || !in->qoff || !in->toff || !in->qlen || !in->tlen || !res || (rev && !begs) || (sb && !subs))))
 		return fail(KSW2AMD_E_PARAM, "local alignment: bad flat batch arguments%s", "");
+	if ((rc = ll_ov_check_ends(ft)) != KSW2AMD_OK) return rc;
 	for (i = 0; i < m * m; ++i) smax = imax(smax, mat[i]);
 	if (ft) smax = imax(smax, 0);
 	for (i = 0; i < n; ++i) {                              /* every argument before anything is uploaded */

@@ -14,14 +14,14 @@
 int ksw2amd_sg_batch(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res)
 {
 	ll_fit_t ft;
-	ft.launch = k2a_shim_launch_sg;
+	ft.launch = k2a_shim_launch_sg; ft.ov = ft.ends = 0;
 	return ll_batch_ex(m, mat, gapo, gape, n, pairs, res, 0, 0, 0, 0, 0, &ft);
 }
 
 int ksw2amd_sg_batch_flat(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lflat_t *in, ksw2amd_lres_t *res)
 {
 	ll_fit_t ft;
-	ft.launch = k2a_shim_launch_sg;
+	ft.launch = k2a_shim_launch_sg; ft.ov = ft.ends = 0;
 	return llf_batch_ex(m, mat, gapo, gape, n, in, res, 0, 0, 0, 0, 0, &ft);
 }
 

@@ -141,7 +141,7 @@ out:
 int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln)
 {
 	ll_fit_t ft;
-	ft.launch = k2a_shim_launch_sg;
+	ft.launch = k2a_shim_launch_sg; ft.ov = ft.ends = 0;
 	return sga_align_ex(km, m, mat, gapo, gape, flag, n, pairs, aln, &ft, k2a_shim_launch_sg_rev, 0);
 }
 
@@ -204,7 +204,7 @@ out:
 int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln)
 {
 	ll_fit_t ft;
-	ft.launch = k2a_shim_launch_sg;
+	ft.launch = k2a_shim_launch_sg; ft.ov = ft.ends = 0;
 	return sga_align_flat_ex(km, m, mat, gapo, gape, flag, n, in, aln, &ft, k2a_shim_launch_sg_rev, 0);
 }
 

@@ -13,7 +13,7 @@
 
 static void sgd_mode(ll_fit_t *ft, ll_dual_t *du, int gapo2, int gape2)
 {
-	ft->launch = k2a_shim_launch_sgd;
+	ft->launch = k2a_shim_launch_sgd; ft->ov = ft->ends = 0;
 	du->gapo2 = gapo2; du->gape2 = gape2; du->fwd = 0; du->pk_reg = K2A_SGD_PK_REG;      /* the forward launch is ft->launch */
 }
 

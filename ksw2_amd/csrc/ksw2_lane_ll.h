@@ -117,7 +117,17 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * (DESIGN.md section 3.22).  cost(l) = min(gapo + l * gape, gapo2 + l * gape2), the pieces as the caller orders them; B = cost(ncols), row -1
  * is B - cost(j + 1) with E' and E2' opened from it, column -1 of the reverse pass is max(B - cost(i + 1), 0), and F2' of column 0 is opened
  * from column -1 like F'.  cost() is non-decreasing, so cost(j + 1) <= B and the arguments above carry over; step() is DUAL's as it stands. */
-template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false>
+/* OV (with FIT, with and without DUAL, never with REV): the overlap mode of ksw2amd_ov_batch / ksw2amd_ovd_batch --
+ * FIT with free query ends, chosen per task by `ends` (K2aLLTask.pad: bit 0 the query's start, bit 1 its end; wavefront-uniform).
+ * Bit 0: row -1 is H(-1, j) = 0, i.e. H' = B in every column with E' = sat(B - oe) (and E2') opened from it, in place of fit_top's ramp.
+ * Every true H(t, j) is still >= -cost(j + 1) >= -B (start in column -1 of row t, insert the query up to j), so the bias and the clamped gap
+ * states hold as they do for FIT.
+ * Bit 1: the cells of the last target row are candidates too.  That row lies in the last generation, in one lane, in strip register
+ * clast = (nrows - 1) % C -- the same register in every lane, so in that generation every lane folds hl[clast] after each step into one
+ * running (maximum, first column) per half (strict >, columns ascending; packed: the row-maximum idiom of the local step, 16-bit column),
+ * and in gen_end the lane that owns row nrows - 1 folds (maximum, nrows - 1, column) into its key beside the last column.  The fold starts
+ * at (0, column 0), which is never above the real cell of column 0 (H' >= 0) and equals it when that cell is 0. */
+template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false, bool OV = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
 	int nrows, ncols, swapped, m, lane, i0;
@@ -129,6 +139,8 @@ struct K2aLaneLL {
 	uint32_t f2[DUAL ? C : 1];                 /* DUAL: F2(i, jj) */
 	uint32_t pa[C], pb[PK ? C : 1], pw[LDSP ? 1 : C];   /* register profile: pen bytes for column codes 0..3 (pa: low half, pb: high
 	                                                     * half), pw: code 4; LDS profile: pa / pb = row code * m */
+	int ends, clast;                           /* OV: the task's free query ends; the last row's strip register in the last generation, else -1 */
+	uint32_t lmax, lcol;                       /* OV: the last row's largest H' so far and its first column */
 	K2aLLKey key[NH];
 	int rl[REV ? NH : 1], cl[REV ? NH : 1];    /* REV: rows / columns of each half's prefix rectangle (0: the half scored 0) */
 
@@ -154,12 +166,14 @@ struct K2aLaneLL {
 			if (DUAL) bias = (uint32_t)k2a_min(par.oe - par.ge + ncols * par.ge, par.oe2 - par.ge2 + ncols * par.ge2) * x;      /* cost(ncols) */
 			if (!REV) for (int h = 0; h < NH; ++h) key[h].s = -1;      /* REV: (0, -1), row -1 of the last column */
 		}
+		if (OV) { ends = tk.pad; clast = -1; lmax = lcol = 0; }
 	}
 
 	/* FIT: B, and row -1 of column k for lane 0 of the first generation: H'(-1, k) and E'(0, k) = sat(H'(-1, k) - oe) */
 	K2A_FN int fit_bias() const { return (int)(bias & (PK ? 0xffffu : 0xffffffffu)); }
 	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e) const
 	{
+		if (OV && (ends & 1)) { h = bias; e = PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0); return; }      /* H(-1, k) = 0 */
 		const int v = (ncols - 1 - k) * (int)(ge & (PK ? 0xffffu : 0xffffffffu)), w = k2a_max(v - (int)(oe & (PK ? 0xffffu : 0xffffffffu)), 0);
 		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u);
 	}
@@ -174,6 +188,11 @@ struct K2aLaneLL {
 	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e, uint32_t &e2) const
 	{
 		const uint32_t mk = PK ? 0xffffu : 0xffffffffu;
+		if (OV && (ends & 1)) {
+			h = bias; e = PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);
+			e2 = PK ? k2a_ll_subs(bias, oe2) : (uint32_t)k2a_max((int)bias - (int)oe2, 0);
+			return;
+		}
 		const int v = fit_bias() - fit_cost(k + 1), w = k2a_max(v - (int)(oe & mk), 0), w2 = k2a_max(v - (int)(oe2 & mk), 0);
 		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u); e2 = (uint32_t)w2 * (PK ? 0x10001u : 1u);
 	}
@@ -189,6 +208,7 @@ struct K2aLaneLL {
 	K2A_FN void gen_begin(int g, const uint8_t *r0, const uint8_t *r1, const uint8_t *tab)
 	{
 		i0 = g * K2A_LL_ROWS + lane * C;
+		if (OV) { clast = ((ends & 2) && (g + 1) * K2A_LL_ROWS >= nrows) ? (nrows - 1) % C : -1; lmax = lcol = 0; }
 		hu_prev = !FIT ? 0u : REV ? fit_left(i0 - 1) : bias;
 		const uint32_t f0 = !FIT ? 0u : PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);      /* FIT: F'(i, 0) = sat(B - oe) */
 #pragma unroll
@@ -290,6 +310,22 @@ struct K2aLaneLL {
 		hout = hl[C - 1];
 		eout = e;
 		e2out = e2;
+		if (OV && clast >= 0) {                    /* the last generation of a task with a free query end: one row's running maximum */
+			uint32_t v = hl[0];
+			switch (clast) {                       /* wavefront-uniform: no indexed register access */
+#define K2A_LL_OVSEL(c) case c: v = hl[c]; break;
+			K2A_LL_OVSEL(1) K2A_LL_OVSEL(2) K2A_LL_OVSEL(3) K2A_LL_OVSEL(4) K2A_LL_OVSEL(5) K2A_LL_OVSEL(6) K2A_LL_OVSEL(7) K2A_LL_OVSEL(8)
+			K2A_LL_OVSEL(9) K2A_LL_OVSEL(10) K2A_LL_OVSEL(11) K2A_LL_OVSEL(12) K2A_LL_OVSEL(13) K2A_LL_OVSEL(14) K2A_LL_OVSEL(15)
+#undef K2A_LL_OVSEL
+			default: break;
+			}
+			if (PK) {
+				const uint32_t d = k2a_ll_subs(v, lmax);                              /* > 0 in a half where v is a new maximum */
+				const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
+				lmax = k2a_ll_max(lmax, v);
+				lcol = (jj2 & mask) | (lcol & ~mask);
+			} else if ((int)v > (int)lmax) { lmax = v; lcol = jj2; }
+		}
 	}
 
 	/* end of a generation: fold the live rows into the lane's key(s).  Every row is looked at (no early exit: the rows past the
@@ -309,6 +345,16 @@ struct K2aLaneLL {
 				key[h].s = take ? s : key[h].s;
 				key[h].te = take ? te : key[h].te;
 				key[h].qe = take ? qe : key[h].qe;
+			}
+		}
+		if (OV && clast >= 0 && (unsigned)(nrows - 1 - i0) < (unsigned)C) {      /* this lane owns the last row: its best cell, beside the last column's */
+#pragma unroll
+			for (int h = 0; h < NH; ++h) {
+				const int s = (int)(PK ? (lmax >> (16 * h)) & 0xffffu : lmax), j = (int)(PK ? (lcol >> (16 * h)) & 0xffffu : lcol);
+				const bool take = k2a_ll_better(s, nrows - 1, j, key[h]);
+				key[h].s = take ? s : key[h].s;
+				key[h].te = take ? nrows - 1 : key[h].te;
+				key[h].qe = take ? j : key[h].qe;
 			}
 		}
 	}

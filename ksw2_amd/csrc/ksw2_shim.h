@@ -228,6 +228,14 @@ int k2a_shim_launch_sgd(int pk, int lds, const K2aLL *par, const K2aLLTask *task
                         uint8_t *scratch, K2aLLRes *res, void *stream);
 int k2a_shim_launch_sgd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                             uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+/* ksw2amd_ov_batch / ksw2amd_ovd_batch: k2a_shim_launch_sg / k2a_shim_launch_sgd with free query ends.  tasks[t].pad
+ * holds the task's `ends` (KSW2AMD_OV_QBEG = 1: row -1 is all zeros; KSW2AMD_OV_QEND = 2: the cells of the last target row are candidates
+ * beside the last column's); res[slot] = (score, qe, te), the largest H, then the smallest te, then the smallest qe.  A packed task with
+ * bit 1 holds a 16-bit column index: ncols <= 65536.  Only ksw2_host_ov.c calls them (the other simulator builds have no such symbols). */
+int k2a_shim_launch_ov(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream);
+int k2a_shim_launch_ovd(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2255,8 +2255,10 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * the whole reversed query, whatever the sign of its score; beg[tk.res[h]] = score of the pass, 0, te_h - (best row), the best row being -1
  * for the empty interval.
  * FIT with DUAL (k2a_sgd_kernel / k2a_sgd_rev_kernel): the same two passes under the two-piece gap cost -- DUAL's chain
- * and 16-byte boundary, FIT's bias and boundary values taken under cost(); lane 0 of the first generation gets E2' of row 0 from fit_top too. */
-template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false>
+ * and 16-byte boundary, FIT's bias and boundary values taken under cost(); lane 0 of the first generation gets E2' of row 0 from fit_top too.
+ * OV (k2a_ov_kernel / k2a_ovd_kernel): FIT with the free query ends of tasks[t].pad -- fit_top's row -1 and, in the last
+ * generation, the running maximum of the last target row; both live in K2aLaneLL<.., OV>, the schedule here is FIT's as it stands. */
+template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false, bool OV = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
             uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg,
@@ -2275,7 +2277,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 	const uint8_t *c0 = seq + tk.coff[0], *c1 = seq + tk.coff[1 & -(int)PK];
 	uint2 *bnd = (uint2*)(scratch + tk.boff);
 	uint4 *bnd2 = (uint4*)(scratch + tk.boff);        /* DUAL: the host sized and aligned the boundary for 16 bytes per column */
-	K2aLaneLL<PK, LDSP, REV, SUB, DUAL, FIT> L;
+	K2aLaneLL<PK, LDSP, REV, SUB, DUAL, FIT, OV> L;
 	L.init(par, tk, lane);
 	int fq[2] = { 0, 0 }, ft[2] = { 0, 0 };        /* REV: the forward end cells */
 	if (REV) {
@@ -2422,6 +2424,24 @@ k2a_sgd_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int nta
                    uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
 {
 	k2a_ll_task<PK, LDSP, true, false, true, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+/* overlap alignment (ksw2amd_ov_batch / ksw2amd_ovd_batch): the semi-global forward pass with the query's ends free
+ * as tasks[t].pad says (bit 0: the start, bit 1: the end).  All eight forms build without scratch */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ov_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+              uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false, false, false, true, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ovd_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+               uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
+{
+	k2a_ll_task<PK, LDSP, false, false, true, true, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
 }
 
 /* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
@@ -3034,6 +3054,37 @@ int k2a_shim_launch_sgd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *
 #endif
 	else if (lds) hipLaunchKernelGGL((k2a_sgd_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	else hipLaunchKernelGGL((k2a_sgd_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* overlap alignment: the grids of k2a_shim_launch_sg / k2a_shim_launch_sgd on tasks whose pad holds the free query ends */
+int k2a_shim_launch_ov(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                       uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "overlap alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ov_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (pk) hipLaunchKernelGGL((k2a_ov_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (lds) hipLaunchKernelGGL((k2a_ov_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_ov_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+int k2a_shim_launch_ovd(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                        uint8_t *scratch, K2aLLRes *res, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "overlap alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ovd_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (pk) hipLaunchKernelGGL((k2a_ovd_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else if (lds) hipLaunchKernelGGL((k2a_ovd_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	else hipLaunchKernelGGL((k2a_ovd_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	CHECK(hipGetLastError());
 	return 0;
 }

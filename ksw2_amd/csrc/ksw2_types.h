@@ -229,7 +229,8 @@ typedef struct K2aLLTask {
 	uint32_t roff[2], coff[2];       /* arena byte offsets of the row / column codes, per half (int32 tasks: [0]) */
 	uint32_t res[2];                 /* result slots of the halves; res[1] == res[0]: one alignment in both halves */
 	int32_t nrows, ncols, swapped;
-	int32_t pad;                     /* ksw2amd_ll_sub_batch: the task's row profile starts at byte 128 * pad of the profile (else 0) */
+	int32_t pad;                     /* ksw2amd_ll_sub_batch: the task's row profile starts at byte 128 * pad of the profile; ksw2amd_ov_batch /
+	                                  * ksw2amd_ovd_batch: the free query ends (KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND); else 0 */
 	uint64_t boff;                   /* byte offset in the scratch of the generation boundary: 8 bytes per column (two-piece: 16; tasks over one generation) */
 } K2aLLTask;                         /* 48 bytes */
 typedef struct K2aLLRes {

@@ -71,7 +71,14 @@ by-hand pattern's host work is reported beside it).  --ktrace: per batch the tim
 under (4, 2), on the pair array of --sg, the three ALTERNATING batch by batch in one process, library calls only in the clock; a parity
 sample against tests/sgd_oracle.c.  --sgd-align: ksw2amd_lld_batch, ksw2amd_sgd_align_batch with KSW_EZ_SCORE_ONLY and with CIGARs, the same
 way.  --ktrace: per batch the time of k2a_lld_kernel, k2a_sg_kernel, k2a_sgd_kernel and k2a_sgd_rev_kernel, the ratios sgd / lld and
-sgd_rev / sgd, and the batch-to-batch spread of k2a_lld_kernel."""
+sgd_rev / sgd, and the batch-to-batch spread of k2a_lld_kernel.
+
+  python tools/scripts/ll_bench.py --workload A --ov [--ktrace kernel_trace.csv] [--out profiles/ov_bench_A.json]
+
+--ov: ksw2amd_ov_batch with both query ends free (overlap alignment) beside ksw2amd_ll_batch and ksw2amd_sg_batch on
+the pair array of --sg, the three ALTERNATING batch by batch in one process, library calls only in the clock; a parity sample against
+tests/ov_oracle.c.  --ktrace: per batch the time of k2a_ll_kernel, k2a_sg_kernel and k2a_ov_kernel, the ratios ov / ll and ov / sg, and the
+batch-to-batch spread of k2a_ll_kernel, which the gap between ov and ll is held against."""
 import argparse
 import ctypes
 import csv
@@ -373,6 +380,78 @@ def main_sg(a, lib, q, t, mat, gapo, gape, cells, form):
                              sg_over_ll=(sum(ks) / len(ks)) / (sum(kl) / len(kl)) if kl and ks else None,
                              ll_resident_gcups=cells / (sum(kl) / len(kl) * 1e-3) / 1e9 if kl else None,
                              sg_resident_gcups=cells / (sum(ks) / len(ks) * 1e-3) / 1e9 if ks else None)
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] else 1
+
+
+def main_ov(a, lib, q, t, mat, gapo, gape, cells, form):
+    """--ov: ksw2amd_ll_batch, ksw2amd_sg_batch and ksw2amd_ov_batch(ends = 3), alternating"""
+    from tests import ov_util as ov
+    ends = ksw2_amd.KSW2AMD_OV_QBEG | ksw2_amd.KSW2AMD_OV_QEND
+    swap = [len(x) > len(y) for x, y in zip(q, t)]
+    q, t = [y if w else x for x, y, w in zip(q, t, swap)], [x if w else y for x, y, w in zip(q, t, swap)]      # target >= query, as --sg
+    n = len(q)
+    L = lib.lib
+    mpp = np.ascontiguousarray(mat, dtype=np.int8).ctypes.data_as(ctypes.POINTER(ctypes.c_int8))
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    res = {k: np.zeros((n, 3), dtype=np.int32) for k in ("ll_batch", "sg_batch", "ov_batch")}
+    rp = lambda x: x.ctypes.data_as(ctypes.POINTER(ksw2_amd.LocalResult))
+    fns = dict(ll_batch=lambda: L.ksw2amd_ll_batch(5, mpp, gapo, gape, n, pairs, rp(res["ll_batch"])),
+               sg_batch=lambda: L.ksw2amd_sg_batch(5, mpp, gapo, gape, n, pairs, rp(res["sg_batch"])),
+               ov_batch=lambda: L.ksw2amd_ov_batch(5, mpp, gapo, gape, ends, n, pairs, rp(res["ov_batch"])))
+    tags = dict(ll_batch="ll: pairs", sg_batch="sg: pairs", ov_batch="ov: pairs")
+    forms = {}
+    os.environ["KSW2AMD_TRACE"] = "1"                          # the warm-ups' form lines
+    for name, fn in fns.items():
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            forms[name] = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if tags[name] in l]
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+    os.environ.pop("KSW2AMD_TRACE")                            # (the binding re-reads the environment in front of every call)
+    times = {k: [] for k in fns}
+    for _ in range(a.reps):                                    # alternating: ll, sg, ov, ll, sg, ov, ...
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    rec = dict(workload=a.workload, mode="ov", ends=ends, pairs=n, cells=cells, ll_form=form, pairs_turned_round=int(sum(swap)),
+               clock="library call only: the pair array is built before it; the three entries alternate batch by batch")
+    for name in fns:
+        ts = times[name]
+        rec[name] = dict(e2e_s=min(ts), e2e_all_s=ts, pairs_per_s=n / min(ts), e2e_gcups=cells / min(ts) / 1e9, forms=forms[name])
+    rec["ov_over_ll_e2e"] = rec["ov_batch"]["e2e_s"] / rec["ll_batch"]["e2e_s"]
+    rec["ov_over_sg_e2e"] = rec["ov_batch"]["e2e_s"] / rec["sg_batch"]["e2e_s"]
+    rec["ll_e2e_spread"] = (max(times["ll_batch"]) - min(times["ll_batch"])) / min(times["ll_batch"])
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    exp = ov.oracle_batch([q[i] for i in idx], [t[i] for i in idx], mat, (gapo, gape), ends, 5)
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = bool((res["ov_batch"][idx] == exp).all())
+    rec["ends_in_last_row_off_the_corner"] = int((res["ov_batch"][:, 1] < np.array([len(x) - 1 for x in q])).sum())
+    rec["scores_differing_from_sg"] = int((res["ov_batch"][:, 0] != res["sg_batch"][:, 0]).sum())
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        mean = lambda v: sum(v) / len(v)
+        kl = trace_batches(a.ktrace, "k2a_ll_kernel", nl(forms["ll_batch"][0]))[1:]        # [0]: the warm-up
+        ks = trace_batches(a.ktrace, "k2a_sg_kernel", nl(forms["sg_batch"][0]))[1:]
+        ko = trace_batches(a.ktrace, "k2a_ov_kernel", nl(forms["ov_batch"][0]))[1:]
+        rec["kernel"] = dict(ll_kernel_ms=kl, sg_kernel_ms=ks, ov_kernel_ms=ko,
+                             ll_kernel_spread=(max(kl) - min(kl)) / min(kl) if kl else None,
+                             ov_over_ll=mean(ko) / mean(kl) if kl and ko else None,
+                             ov_over_sg=mean(ko) / mean(ks) if ks and ko else None,
+                             ov_below_ll_by_more_than_the_spread=bool(max(ko) < min(kl) and (mean(kl) - mean(ko)) > (max(kl) - min(kl))) if kl and ko else None,
+                             ov_resident_gcups=cells / (mean(ko) * 1e-3) / 1e9 if ko else None)
     print(json.dumps(rec))
     if a.out:
         with open(a.out, "w") as fo:
@@ -753,6 +832,7 @@ def main():
     ap.add_argument("--sg-align", action="store_true", help="ksw2amd_sg_batch, ksw2amd_sg_align_batch (SCORE_ONLY and with CIGARs) and the by-hand pattern (sg_batch, host reversal, two ksw2amd_extz_batch calls) on the same pair array, alternating")
     ap.add_argument("--sgd", action="store_true", help="ksw2amd_sgd_batch under (4, 2, 24, 1) beside ksw2amd_lld_batch and ksw2amd_sg_batch on the pair array of --sg, alternating, library calls only in the clock")
     ap.add_argument("--sgd-align", action="store_true", help="ksw2amd_lld_batch and ksw2amd_sgd_align_batch (SCORE_ONLY and with CIGARs) on the same pair array, alternating")
+    ap.add_argument("--ov", action="store_true", help="ksw2amd_ov_batch with both query ends free beside ksw2amd_ll_batch and ksw2amd_sg_batch on the pair array of --sg, alternating, library calls only in the clock")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -769,6 +849,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.ov:
+        return main_ov(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sgd or a.sgd_align:
         return main_sgd(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sg_align:
