@@ -60,6 +60,7 @@
 	X(NO_PKMP) \
 	X(NO_RB) \
 	X(NO_SHARED_UP) \
+	X(PAIR_MAX) \
 	X(PIN) \
 	X(PK_FIRST) \
 	X(POOL_MIN) \

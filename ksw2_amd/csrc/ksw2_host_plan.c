@@ -1130,6 +1130,23 @@ ksw2amd_plan_t *plan_create_ex(int dual, int scalar, const ksw2amd_scoring_t *sc
 			            * 512 wavefronts: 1 063 GCUPS deferred against 1 241 from registers) */
 			           (forced < 0 ? k2a_pkcfg_G[c->cfg] == 64 && (k2a_shim_simd_count() > 0 ? 2 * (int64_t)(g_probe_tasks ? g_probe_tasks : c->count) >= 3 * (int64_t)k2a_shim_simd_count()
 			                                                                                      : (g_probe_tasks ? g_probe_tasks : c->count) >= 32) : forced);
+			/* Pair-maximum form (K2aLanePk PM, K2A_PAIR_MAX): a deferred one-group class keeps one running maximum per pair of rows and
+			 * its fold freezes a book `slack` = delta + q early (ksw2_lane_pkfold.h, k2a_pkfold_task_pm).  It is exact for any Z-drop, but
+			 * under a threshold close to the slack healthy reads freeze and go through the third pass: only classes whose pairs all
+			 * have zdrop < 0 or zdrop >= 4 * slack take it (preset scoring 2 / 4 / 4 / 2: 48).  Measured on 8 192 reads of 10 k, 5 % / 6 %
+			 * errors, pair form against per-row form (profiles/stripmax_ab.txt): zdrop 24: 69.9 against 57.9 ms, 32: 54.5 against 55.4
+			 * (both forms freeze most reads there), 48 and above: 16.9 against 17.3.  KSW2AMD_PAIR_MAX=0: never */
+			c->sc.pk_pm = 0;
+			if (K2A_PAIR_MAX_ON && c->defer && k2a_pkcfg_G[c->cfg] == 64 && pkinfo[c->generic].ok > 0 && !(ENV(PAIR_MAX) && *ENV(PAIR_MAX) && atoi(ENV(PAIR_MAX)) == 0)) {      /* (an empty value is no value, as for KSW2AMD_DEFER) */
+				const pkinfo_t *pi_ = &pkinfo[c->generic];
+				const int slack = imax(imax(pi_->smax + q + e, -pi_->smin), q + e) + q;
+				int okz = slack > 0;
+				for (i = 0; i < 2 * c->count && okz; ++i) {
+					const int z = p->h_pairs[p->h_order[c->first + i]].zdrop;
+					if (z >= 0 && z < 4 * slack) okz = 0;
+				}
+				if (okz) c->sc.pk_pm = slack;
+			}
 		}
 		if (g_probe_tasks) { free(pk_ok); free(solo_ok); return p; }      /* the class is known: nothing was copied, allocated on the device or uploaded */
 		for (lo = 0; lo < 2; ++lo) {                       /* 0: size it, 1: lay it out */
@@ -1163,7 +1180,7 @@ ksw2amd_plan_t *plan_create_ex(int dual, int scalar, const ksw2amd_scoring_t *sc
 				if (ck_total > ((size_t)1 << 30) && forced < 0) {            /* big: only if it fits beside the rest of the device's tenants */
 					size_t free_b = 0, total_b = 0;
 					if (k2a_shim_mem_info(&free_b, &total_b) || ck_total > (free_b + thread_cached_device_bytes()) / 10 * 6) {
-						for (k = 0; k < p->ncls; ++k) p->cls[k].defer = 0;
+						for (k = 0; k < p->ncls; ++k) { p->cls[k].defer = 0; p->cls[k].sc.pk_pm = 0; }
 						ck_total = 0;
 						break;
 					}
@@ -1757,10 +1774,11 @@ int ksw2amd_plan_describe(const ksw2amd_plan_t *p, char *buf, int cap)
 		const int G = k->solo ? 64 : k->pk ? k2a_pkcfg_G[k->cfg] : k2a_cfg_G[k->cfg], C = k->solo ? 2 * K2A_SOLO_ROWS(k->mode == K2A_MODE_SCORE) : k->pk ? k2a_pkcfg_C[k->cfg] : k2a_cfg_C[k->cfg];
 		const int form = k->defer ? 3 : k->solo ? 0 : k->pk ? (k->cfg == K2A_PKCFG_MP ? 0 : k2a_shim_pk_form(k->cfg, p->dual, k->mode, k->nomax, k->count))
 		                                     : (k->cfg == K2A_CFG_MP ? k2a_shim_mp_form(p->dual, k->mode, k->count) : 0);
-		len += snprintf(buf + len, (size_t)(cap - len), "kernel=%s G=%d C=%d gaps=%d mode=%s rebased=%d nomax=%d generic=%d form=%s tasks=%d uniform=%d wire4=%d tn=%d base=%d\n",
+		len += snprintf(buf + len, (size_t)(cap - len), "kernel=%s G=%d C=%d gaps=%d mode=%s rebased=%d nomax=%d generic=%d form=%s tasks=%d uniform=%d wire4=%d tn=%d base=%d pairmax=%d\n",
 		                kind, G, C, p->dual ? 2 : 1, mode_name[k->mode], k->rb, k->nomax, k->generic, form_name[form], k->count, p->uni ? 1 : 0,
 		                p->up_state ? p->up_state->wire4 : 0, (k->pk || k->solo) && k->sc.pk_tn1 ? 1 : 0,       /* tn: target wildcards are rows of this packed class (K2aScoring.pk_tn1) */
-		                (k->pk || k->solo) ? k->sc.pk_base : 0);                                                /* base: what the class's profile bytes are short of (K2aScoring.pk_base) */
+		                (k->pk || k->solo) ? k->sc.pk_base : 0,                                                 /* base: what the class's profile bytes are short of (K2aScoring.pk_base) */
+		                k->defer ? k->sc.pk_pm : 0);                                                            /* pairmax: the freeze slack of a deferred class in the pair-maximum form (K2aScoring.pk_pm), 0 = per-row form */
 	}
 	return p->ncls;
 }

@@ -347,8 +347,21 @@ struct K2aRowPredUniform {
 /* TN: the build for wavefront-tasks whose targets hold a wildcard code (K2aScoring.pk_tn1; the kernels look at their targets first and
  * take this build or the plain one as a whole -- a test inside the plain step costs every batch 1-3 %, 10 % at one wavefront per SIMD:
  * profiles/r6_ab_tn.txt) */
-template<int G, int C, bool DUAL, int MODE = K2A_MODE_SCORE, bool RB = false, bool NOMAX = false, int LDSROW_ = 0, bool DEFER = false, bool TN = false>
+/* PM ("pair maximum"; deferred fills whose strip ends are folded behind the loop, K2A_PAIR_MAX): ONE running maximum per pair of rows
+ * (2p, 2p + 1), folded per step with one v_pk_maximum3_f16 out of registers the step has just written -- eight instructions and eight
+ * registers for sixteen rows instead of sixteen v_pk_max_u16 and sixteen registers.  The two rows carry different biases (e * i), so
+ * their H - q cannot be compared as they stand; but the odd row's F register holds max(F, H - q) - e, i.e. at least its H - q in the
+ * EVEN row's bias, and over the steps of a strip its maximum is exactly the maximum of the odd row's H - q - e (F decays by e per step
+ * and never exceeds a cell of its own row).  So
+ *     pmax[p] = max over the strip's steps of max3(pmax[p], hl[2p], f[2p + 1])      (both read after the step's update)
+ * is the larger of the two rows' maxima, as H - q in the bias of row 2p.  One exception: a row that starts at column 0 enters the
+ * strip with its border F(i, 0) = H(i, -1) - q - e in f, which is no cell; it can lift an odd row's part by at most q above the row's
+ * true maximum (H(i, 0) >= F(i, 0)) and stands for a negative H, so it never becomes a book's maximum (books start at 0) and the fold's
+ * freeze test allows for it (K2aScoring.pk_pm).  Dead rows hold -inf in both registers.  rmax(c) / set_rmax(c) address the pair's
+ * register; the exact row and its column come from the second pass (k2a_argmax_kernel), which runs the per-row code. */
+template<int G, int C, bool DUAL, int MODE = K2A_MODE_SCORE, bool RB = false, bool NOMAX = false, int LDSROW_ = 0, bool DEFER = false, bool TN = false, bool PM = false>
 struct K2aLanePk {
+	static_assert(!PM || (DEFER && !NOMAX && !DUAL && MODE == K2A_MODE_SCORE && LDSROW_ != 1 && C % 4 == 0 && K2A_HL_OPEN), "pair maxima: deferred exact score-only single-gap fills in the open form");
 	enum { NIB = K2A_PK_NIBBLES(C, DUAL), TBWORDS = NIB ? C / 4 : C / 2 };
 	/* NIB (single gap, 16 rows): direction flags of 4 bits (k2a_dir_flags: bit 0 E wins, 1 F wins, 2 / 3 = the E / F gap leaving the
 	 * cell is an extension) -- four consecutive rows per 16-bit half (row 4g at bits 3-0 ... row 4g+3 at bits 15-12), word g of a
@@ -376,14 +389,14 @@ struct K2aLanePk {
 	/* rows */
 	enum { LDSROW = LDSROW_ == 1,       /* row maxima, arg-max columns and target selectors in LDS */
 	       LDSTC = LDSROW_ != 0 };      /* 2: only the target selectors */
-	k2a_pk hl[C], f[C], f2[DUAL ? C : 1], rmax_[(NOMAX || LDSROW) ? 1 : C], rmj_[(NOMAX || LDSROW || DEFER) ? 1 : C];       /* hl, f, f2, rmax and the ports above: offset form */
+	k2a_pk hl[C], f[C], f2[DUAL ? C : 1], rmax_[(NOMAX || LDSROW) ? 1 : PM ? C / 2 : C], rmj_[(NOMAX || LDSROW || DEFER) ? 1 : C];       /* hl, f, f2, rmax and the ports above: offset form */
 	k2a_pk tc_[LDSTC ? 1 : C];                                   /* per row: the v_perm_b32 selector of the rows' target codes {A, B} (K2A_TSEL_BASE) */
 	uint32_t *lrow;                                              /* LDSROW: this lane's column of the wavefront's [3][C][64] block; selectors only: [C][64] */
 	enum { TCROW = LDSROW ? 2 : 0 };
-	K2A_FN k2a_pk rmax(int c) const { return LDSROW ? lrow[(0 * C + c) * 64] : rmax_[(NOMAX || LDSROW) ? 0 : c]; }
+	K2A_FN k2a_pk rmax(int c) const { return LDSROW ? lrow[(0 * C + c) * 64] : rmax_[(NOMAX || LDSROW) ? 0 : PM ? c >> 1 : c]; }
 	K2A_FN k2a_pk rmj(int c) const { return DEFER ? 0u : LDSROW ? lrow[(1 * C + c) * 64] : rmj_[(NOMAX || LDSROW) ? 0 : c]; }
 	K2A_FN k2a_pk tc(int c) const { return LDSTC ? lrow[(TCROW * C + c) * 64] : tc_[LDSTC ? 0 : c]; }
-	K2A_FN void set_rmax(int c, k2a_pk v) { if (LDSROW) lrow[(0 * C + c) * 64] = v; else rmax_[(NOMAX || LDSROW) ? 0 : c] = v; }
+	K2A_FN void set_rmax(int c, k2a_pk v) { if (LDSROW) lrow[(0 * C + c) * 64] = v; else rmax_[(NOMAX || LDSROW) ? 0 : PM ? c >> 1 : c] = v; }
 	K2A_FN void set_rmj(int c, k2a_pk v) { if (DEFER) return; if (LDSROW) lrow[(1 * C + c) * 64] = v; else rmj_[(NOMAX || LDSROW) ? 0 : c] = v; }
 	K2A_FN void set_tc(int c, k2a_pk v) { if (LDSTC) lrow[(TCROW * C + c) * 64] = v; else tc_[LDSTC ? 0 : c] = v; }
 
@@ -461,7 +474,7 @@ struct K2aLanePk {
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			hl[c] = neg; f[c] = neg; if (DUAL) f2[c] = neg;
-			if (!NOMAX) set_rmax(c, neg);                        /* the arg-max column is written with the row's first live cell */
+			if (!NOMAX && !(PM && (c & 1))) set_rmax(c, neg);    /* the arg-max column is written with the row's first live cell */
 		}
 		const int hcorner = k2a_border<DUAL>(sc, i0) + sc.e * (i0 - 1);   /* H(i0-1,-1), carrying the bias of row i0-1 */
 		const int hq = k2a_hl_q(sc);                                      /* hl, hd0, hu_prev hold H - hq */
@@ -580,7 +593,8 @@ struct K2aLanePk {
 				h = rp.pick(c, h, neg);
 				/* running row maximum: ties to the last column (keep the old arg-max only where h < max), except
 				 * extz + RIGHT + CIGAR where the first column wins (take the new one only where max < h); SURVEY 8a rule 3 */
-				if (!NOMAX && DEFER) set_rmax(c, k2a_pk_maxu(rmax(c), h));       /* the column comes from k2a_argmax_kernel */
+				if (!NOMAX && DEFER && PM) {}                                    /* below, once per pair */
+				else if (!NOMAX && DEFER) set_rmax(c, k2a_pk_maxu(rmax(c), h));  /* the column comes from k2a_argmax_kernel */
 				else if (!NOMAX) {
 					const k2a_pk rm = rmax(c), rj = rmj(c);
 					if (!DUAL && MODE == K2A_MODE_RIGHT) set_rmj(c, k2a_pk_selv(k2a_pk_sign(k2a_pk_sub(rm, h)), jjpk, rj));
@@ -595,6 +609,7 @@ struct K2aLanePk {
 				else if (MODE == K2A_MODE_RIGHT) { x1 = k2a_pk_sub(e, t); x2 = k2a_pk_sub(fc, t); }        /* extension at least as good as opening */
 				e = k2a_pk_maxu(e, t);
 				f[c] = k2a_sub32(k2a_pk_maxu(fc, t), ge);
+				if (PM && (c & 1)) set_rmax(c, k2a_pk_max3u(rmax(c), hl[c - 1], f[c]));       /* rows c - 1 and c in the bias of row c - 1 (see PM) */
 				if (DUAL) {
 					const k2a_pk t2 = k2a_sub32(h, gq2);
 					if (MODE == K2A_MODE_LEFT) { x3 = k2a_pk_sub(t2, e2); x4 = k2a_pk_sub(t2, f2[c]); }

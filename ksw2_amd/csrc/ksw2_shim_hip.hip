@@ -348,7 +348,7 @@ __device__ __forceinline__ void k2a_cptab_fill(const K2aScoring &sc, uint32_t *t
 /* Packed-int16 resident fill: two same-shape alignments per lane group (ksw2_lane_pk.h).  k2a_fill_pk_body = one wavefront-task, in the
  * plain build or the TN one (target wildcard rows, see k2a_scan_codes); scan = what the task's look at its targets found (TN: bit 1 per
  * lane = a code above 4 in its group's targets). */
-template<int G, int C, bool DUAL, int MODE, bool RB, bool NOMAX, int LDSROW, bool DEFER, bool TN>
+template<int G, int C, bool DUAL, int MODE, bool RB, bool NOMAX, int LDSROW, bool DEFER, bool TN, bool PM = false>
 __device__ __forceinline__ void
 k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const uint32_t *__restrict__ order2, int ntasks,
                  const uint8_t *__restrict__ seq, uint8_t *__restrict__ tb, K2aResult *__restrict__ res,
@@ -356,7 +356,7 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
                  K2aBook (*book)[64 / G][2], uint32_t *stage_w, uint32_t *lrows, uint32_t (*cptab)[8], uint4 *tbstage, unsigned long long *tbruns)
 {
 	constexpr int NG = 64 / G;
-	typedef K2aLanePk<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, TN> Lane;
+	typedef K2aLanePk<G, C, DUAL, MODE, RB, NOMAX, LDSROW, DEFER, TN, PM> Lane;
 	constexpr int LROW_WORDS = LDSROW == 1 ? K2A_PK_LDSROW_WORDS(C) : LDSROW == 2 ? K2A_PK_LDSCODE_WORDS(C) : 0;
 	constexpr int WB = Lane::TBWORDS * 4;
 	constexpr bool STAGED = MODE != K2A_MODE_SCORE && (WB == 16 || WB == 32);
@@ -407,6 +407,7 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 	/* ... and nothing inside the loop reads the books there, so the strip ends are folded into them once, behind the loop
 	 * (ksw2_lane_pkfold.h): the lane whose strip ends stores the strip's record and is done */
 	constexpr bool FOLD = K2A_FOLD_AFTER != 0 && DEFER && NG == 1 && !NOMAX && MODE == K2A_MODE_SCORE;
+	static_assert(!PM || FOLD, "pair maxima: the fills that fold their strip ends behind the loop");
 	K2aRowMasks<C> RM;
 	RM.reset();
 	Stage ST;
@@ -495,8 +496,13 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 				 * strips save half the stores */
 				if (nfin) {
 					uint4 *r4 = (uint4*)(ckrec + (size_t)L.S * K2A_CK_REC_WORDS(C));
+					if (PM) {                                      /* the pairs' maxima: the record's first C / 2 dwords */
 #pragma unroll
-					for (int c = 0; c < C; c += 4) r4[c / 4] = make_uint4(L.rmax(c), L.rmax(c + 1), L.rmax(c + 2), L.rmax(c + 3));
+						for (int c = 0; c < C; c += 8) r4[c / 8] = make_uint4(L.rmax(c), L.rmax(c + 2), L.rmax(c + 4), L.rmax(c + 6));
+					} else {
+#pragma unroll
+						for (int c = 0; c < C; c += 4) r4[c / 4] = make_uint4(L.rmax(c), L.rmax(c + 1), L.rmax(c + 2), L.rmax(c + 3));
+					}
 					if (k2a_pkfold_strip_reaches<C>(L.S, L.qlen, L.tlen, L.w)) {
 #pragma unroll
 						for (int c = 0; c < C; c += 4) r4[(C + c) / 4] = make_uint4(L.hl[c], L.hl[c + 1], L.hl[c + 2], L.hl[c + 3]);
@@ -535,7 +541,8 @@ k2a_fill_pk_body(const K2aScoring &sc, const K2aPair *__restrict__ pairs, const 
 		 * narrowest scope that orders them within a CU, once per task */
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-		if (ckon) k2a_pkfold_task<C, 1>(sc, ckrec, ckhd, L.nstrips, L.qlen, L.tlen, L.tlen_full, L.w, zdropA, zdropB, bkA, bkB, stage_w, lane);
+		if (ckon && PM) k2a_pkfold_task_pm<C, 1>(sc, ckrec, ckhd, L.nstrips, L.qlen, L.tlen, L.tlen_full, L.w, zdropA, zdropB, sc.pk_pm, bkA, bkB, stage_w, lane);
+		else if (ckon) k2a_pkfold_task<C, 1>(sc, ckrec, ckhd, L.nstrips, L.qlen, L.tlen, L.tlen_full, L.w, zdropA, zdropB, bkA, bkB, stage_w, lane);
 		__builtin_amdgcn_wave_barrier();
 	} else if (!zseq) {
 		/* merge the lane-local bests of each group; the lane that finished the last target row adds mte / score */
@@ -616,6 +623,45 @@ k2a_fill_pk_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const
 	}
 }
 
+#if K2A_PAIR_MAX_ON
+/* The deferred exact score-only fills of one group per wavefront, (64, 8) and (64, 16), in the pair-maximum form (K2aLanePk PM): what
+ * k2a_fill_pk_kernel<64, C, false, 0, RB, false, LDSROW, true, QUEUE> does, around the PM build of the body.  A kernel of its own, so
+ * that no other instantiation's text -- or name -- changes with it. */
+template<int C, bool RB, int LDSROW, bool QUEUE>
+__global__ void __launch_bounds__(64 * K2A_WPB, LDSROW == 2 ? 3 : 1)
+k2a_fill_pkpm_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const uint32_t *__restrict__ order2, int ntasks,
+                     const uint8_t *__restrict__ seq, uint8_t *__restrict__ tb, K2aResult *__restrict__ res, K2aQueueDesc *qd)
+{
+	static_assert(LDSROW == 0 || LDSROW == 2, "score-only: the rows' maxima stay in registers");
+	__shared__ K2aBook book[K2A_WPB][1][2];
+	__shared__ uint32_t stage[K2A_WPB][64 * 5];            /* the fold's exchange buffer (K2A_PKFOLD_XB_WORDS) */
+	const int lane = threadIdx.x & 63, wave = k2a_wave_id<(C <= 8 || LDSROW != 0)>();
+	const int wt = blockIdx.x * K2A_WPB + wave;
+	if (blockIdx.x == 0 && threadIdx.x == 0) {              /* the list of frozen books: empty */
+		uint32_t *zlist = (uint32_t*)(tb + pairs[order2[0]].tb_off) - K2A_ZLIST_WORDS(ntasks);
+		__hip_atomic_store(&zlist[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	if (QUEUE && !k2a_queue_wait(qd, wt)) return;
+	__shared__ uint32_t lrows[LDSROW ? K2A_WPB * K2A_PK_LDSCODE_WORDS(C) : 1];
+	__shared__ uint32_t cptab[K2A_WPB][8];
+	__shared__ uint4 tbstage[1];
+	__shared__ unsigned long long tbruns[1];
+	/* the task's look at its targets (k2a_scan_codes), then the plain or the TN build of the body */
+	uint32_t scan = 0;
+	const bool scan_on = sc.pk_tn1 != 0;
+	if (scan_on && wt < ntasks) {
+		const K2aPair pa = pairs[order2[2 * wt]], pb = pairs[order2[2 * wt + 1]];
+		scan = k2a_scan_codes<64>(seq + pa.toff, pa.tlen_full, lane) | k2a_scan_codes<64>(seq + pb.toff, pb.tlen_full, lane);
+	}
+	const uint64_t m1 = __builtin_amdgcn_ballot_w64((scan & 1u) != 0), m2 = __builtin_amdgcn_ballot_w64((scan & 2u) != 0);
+	scan = (m1 ? 1u : 0u) | (m2 ? 2u : 0u);
+	if (m1 != 0 || sc.pk_base != 0)
+		k2a_fill_pk_body<64, C, false, K2A_MODE_SCORE, RB, false, LDSROW, true, true, true>(sc, pairs, order2, ntasks, seq, tb, res, wt, wave, lane, 0, lane, scan_on, scan, book, stage[wave], lrows, cptab, tbstage, tbruns);
+	else
+		k2a_fill_pk_body<64, C, false, K2A_MODE_SCORE, RB, false, LDSROW, true, false, true>(sc, pairs, order2, ntasks, seq, tb, res, wt, wave, lane, 0, lane, scan_on, scan, book, stage[wave], lrows, cptab, tbstage, tbruns);
+}
+#endif
+
 /* Second pass of the deferred arg-max (K2aLanePk, DEFER): three jobs per task -- the strip that holds alignment A's maximum,
  * the one that holds B's, and the strip of the last target row (mte_q of both) -- one job per LANE: every lane re-runs its strip
  * with the ordinary exact lane code (arg-max on), its top inputs read back from the checkpoint stream, its bases from the strip's
@@ -692,6 +738,102 @@ k2a_argmax_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const 
 		zlist[1 + at] = (uint32_t)task * 2u + (uint32_t)which;
 	}
 }
+
+#if K2A_PAIR_MAX_ON
+/* ... behind a fill in the pair-maximum form (K2aLanePk PM; k2a_fill_pkpm_kernel): the same three jobs with the same per-row lane code, and
+ * in addition jobs 0 and 1 find the ROW of the maximum in the strip they re-ran -- the fold left max_t at the first row of the pair --
+ * and job 2 writes mte, the last target row's own maximum, next to mte_q.  This pass runs before the third one, so a frozen book
+ * reaches k2a_zscan_kernel with its exact max, max_t and max_q.  A kernel of its own: k2a_argmax_kernel keeps its text and registers. */
+template<int C, bool RB>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_argmax_pm_kernel(const K2aScoring sc, const K2aPair *__restrict__ pairs, const uint32_t *__restrict__ order2, int ntasks,
+                  const uint8_t *__restrict__ seq, uint8_t *__restrict__ ck, K2aResult *__restrict__ res, const K2aQueueDesc *qd)
+{
+	constexpr int G = 64, NG = 1;
+	__shared__ uint32_t rows[64 * K2A_WPB][2 * C + 1];      /* the re-run strips' row maxima and arg-max columns, one buffer per lane; an odd stride */
+	/* behind a streamed fill that was abandoned (k2a_queue_wait: abort raised, or wavefront-tasks that never started): the result
+	 * records and checkpoint blocks of the tasks the fill never ran hold whatever the recycled buffers held before -- a stale max_t
+	 * would index strips megabytes past the task's block.  Nothing to do here then: the host repeats the whole plan unstreamed. */
+	if (qd && (__hip_atomic_load(&qd->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ||
+	           __hip_atomic_load(&qd->next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != qd->nwt)) return;
+	typedef K2aLanePk<G, C, false, K2A_MODE_SCORE, RB, false, 0, false, true> Lane;      /* (the TN build: a re-run strip may hold a target wildcard row) */
+	const int job = blockIdx.x * (64 * K2A_WPB) + threadIdx.x;
+	const int task = job / 3, which = job - 3 * task;
+	bool go = task < ntasks;
+	const bool live = go;
+	const uint32_t piA = order2[go ? 2 * task : 0], piB = order2[go ? 2 * task + 1 : 0];
+	const K2aPair prA = pairs[piA], prB = pairs[piB];
+	const bool inexA = res[piA].pad[1] != 0, inexB = res[piB].pad[1] != 0;
+	int row = -1;
+	if (go) {
+		if (which == 0) row = res[piA].max_t;
+		else if (which == 1) row = piB == piA ? -1 : res[piB].max_t;
+		else row = (prA.tlen == prA.tlen_full && !(inexA && inexB)) ? prA.tlen_full - 1 : -1;
+	}
+	go = go && row >= 0;
+	const int S = go ? row / C : 0, grp = task % NG;
+	__shared__ uint32_t cptab[K2A_WPB][8];
+	k2a_cptab_fill(sc, cptab[threadIdx.x >> 6], (int)(threadIdx.x & 63));
+	Lane L;
+	L.lrow = 0;
+	L.setup(prA, prB, seq, S % G, go, cptab[threadIdx.x >> 6]);
+	L.Snext = S;
+	L.schedule_next();
+	const int kbeg = L.knext;
+	const uint8_t *blk = ck + prA.tb_off;
+	if (go) L.do_init(sc, 0, 0, (const K2aCkHead*)(blk + (size_t)prA.bnd_off * K2A_CK_STEP_BYTES) + (size_t)grp * prA.cig_off + S);
+	K2A_SYNC_WN(L);
+	const int n = go ? L.kfin - kbeg + 1 : 0;
+	const uint2 *st = (const uint2*)blk + (grp * G + S % G);
+	for (int t = 0; __builtin_amdgcn_ballot_w64(t < n) != 0; ++t) {
+		if (t < n) {
+			const int k = kbeg + t;
+			const uint2 in = st[(size_t)k * 64];
+			const int jc = min(max(k - L.koff, 0), L.qlen - 1);
+			L.set_qb(k2a_pair16(L.qa[jc], L.qbp[jc]));
+			uint32_t tw[Lane::TBWORDS];
+			L.step(sc, k, in.x, in.y, 0u, tw);
+		}
+	}
+	if (go) {
+		/* the strip's row maxima (plain int16 halves, row bias on) and arg-max columns out of the registers, then rolled loops: nothing
+		 * of this is alive in the step loop above */
+		uint32_t *rb = rows[threadIdx.x];
+#pragma unroll
+		for (int cc = 0; cc < C; ++cc) { rb[cc] = k2a_ofs_off(L.rmax(cc)); rb[C + cc] = L.rmj(cc); }
+		int c = row - S * C;
+		if (which != 2) {
+			/* max_t names the PAIR's first row.  The row is the first of the strip's rows, in front of a frozen book's freeze row, whose
+			 * own maximum is the largest (= the book's maximum: the fold moved it to this strip last) -- strictly greater in row
+			 * order, as fin_fast.  Rows compare without their bias; the strip's base is common to them */
+			const int sh = which == 1 ? 16 : 0;
+			const int lim = (which == 0 ? inexA : inexB) ? res[which == 0 ? piA : piB].rows_done - 1 : prA.tlen;
+			int best = (int)0x80000000;
+#pragma nounroll
+			for (int cc = 0; cc < C; ++cc) {
+				const int v = (int)(int16_t)(rb[cc] >> sh) - sc.e * cc;
+				if (S * C + cc < lim && v > best) { best = v; c = cc; }
+			}
+			if (which == 0) res[piA].max_t = S * C + c; else res[piB].max_t = S * C + c;
+		}
+		const k2a_pk v = rb[C + c], vm = rb[c];
+		if (which == 0) res[piA].max_q = (int)(v & 0xffffu);
+		else if (which == 1) res[piB].max_q = (int)(v >> 16);
+		else {                                                 /* ... and mte holds the pair's maximum: the last target row's own */
+			if (!inexA) { res[piA].mte_q = (int)(v & 0xffffu); res[piA].mte = k2a_pk_lo(vm) + L.baseA - sc.e * row; }
+			if (piB != piA && !inexB) { res[piB].mte_q = (int)(v >> 16); res[piB].mte = k2a_pk_hi(vm) + L.baseB - sc.e * row; }
+		}
+	}
+	/* frozen books: into the list of the third pass, { task, half } (the list lies in front of the class's first checkpoint block;
+	 * the fill kernel zeroed its counter) */
+	if (live && ((which == 0 && inexA) || (which == 1 && inexB && piB != piA))) {
+		uint32_t *zlist = (uint32_t*)(ck + pairs[order2[0]].tb_off) - K2A_ZLIST_WORDS(ntasks);
+		const uint32_t at = __hip_atomic_fetch_add(&zlist[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		zlist[1 + at] = (uint32_t)task * 2u + (uint32_t)which;
+	}
+}
+
+#endif
 
 /* Third pass of the deferred arg-max: the alignments whose book the fill froze at a row where a Z-drop could not be ruled out
  * without the arg-max columns (max - H > zdrop there; no earlier row came that far).  The reference's test (ksw2.h:191-207) also
@@ -2160,9 +2302,18 @@ static const fill_pk_fn g_fill_pkq_ldscodes[3][2][2] = { LDSCODEQ_SET(64, 16), L
 static const fill_pk_fn g_fill_pk_defer[4][2] = { DEFER_ROW(8, 18, 0), DEFER_ROW(16, 8, 2), DEFER_ROW(64, 8, 0), DEFER_ROW(64, 16, 2) };
 #define DEFERQ_ROW(G, C, LR) { k2a_fill_pk_kernel<G, C, false, 0, false, false, LR, true, true>, k2a_fill_pk_kernel<G, C, false, 0, true, false, LR, true, true> }
 static const fill_pk_fn g_fill_pkq_defer[4][2] = { DEFERQ_ROW(8, 18, 0), DEFERQ_ROW(16, 8, 2), DEFERQ_ROW(64, 8, 0), DEFERQ_ROW(64, 16, 2) };
+/* ... and the one-group geometries in the pair-maximum form (K2aLanePk PM; K2aScoring.pk_pm != 0): [(64, 8) | (64, 16)][rebased] */
+#if K2A_PAIR_MAX_ON
+#define DEFERPM_ROW(C, LR, Q) { k2a_fill_pkpm_kernel<C, false, LR, Q>, k2a_fill_pkpm_kernel<C, true, LR, Q> }
+static const fill_pk_fn g_fill_pk_defer_pm[2][2] = { DEFERPM_ROW(8, 0, false), DEFERPM_ROW(16, 2, false) };
+static const fill_pk_fn g_fill_pkq_defer_pm[2][2] = { DEFERPM_ROW(8, 0, true), DEFERPM_ROW(16, 2, true) };
+#endif
 typedef void (*argmax_fn)(const K2aScoring, const K2aPair*, const uint32_t*, int, const uint8_t*, uint8_t*, K2aResult*, const K2aQueueDesc*);
 #define ARGMAX_ROW(G, C) { k2a_argmax_kernel<G, C, false>, k2a_argmax_kernel<G, C, true> }
 static const argmax_fn g_argmax[4][2] = { ARGMAX_ROW(8, 18), ARGMAX_ROW(16, 8), ARGMAX_ROW(64, 8), ARGMAX_ROW(64, 16) };
+#if K2A_PAIR_MAX_ON
+static const argmax_fn g_argmax_pm[2][2] = { { k2a_argmax_pm_kernel<8, false>, k2a_argmax_pm_kernel<8, true> }, { k2a_argmax_pm_kernel<16, false>, k2a_argmax_pm_kernel<16, true> } };
+#endif
 typedef void (*zscan_fn)(const K2aScoring, const K2aPair*, const uint32_t*, int, const uint8_t*, const uint8_t*, K2aResult*, const K2aQueueDesc*);
 #define ZSCAN_ROW(G, C) { k2a_zscan_kernel<G, C, false>, k2a_zscan_kernel<G, C, true> }
 static const zscan_fn g_zscan[4][2] = { ZSCAN_ROW(8, 18), ZSCAN_ROW(16, 8), ZSCAN_ROW(64, 8), ZSCAN_ROW(64, 16) };
@@ -2710,10 +2861,20 @@ int k2a_shim_launch_fill_pk(int cfg, int dual, int mode, int rebased, int nomax,
 		/* deferred arg-max: the fill streams its checkpoints into `tb` (block offsets in K2aPair.tb_off / bnd_off / cig_off),
 		 * the second pass fills in max_q / mte_q */
 		if (cfg >= K2A_PKCFG_MP || dual || mode != K2A_MODE_SCORE || nomax || !tb) { snprintf(g_err, sizeof(g_err), "bad deferred arg-max class"); return -1; }
-		const fill_pk_fn fn = (qd ? g_fill_pkq_defer : g_fill_pk_defer)[cfg][rebased ? 1 : 0];
+		fill_pk_fn fn = (qd ? g_fill_pkq_defer : g_fill_pk_defer)[cfg][rebased ? 1 : 0];
+		argmax_fn fn2 = g_argmax[cfg][rebased ? 1 : 0];
+#if K2A_PAIR_MAX_ON
+		if (sc->pk_pm != 0) {                                  /* the class qualified for the pair-maximum form (ksw2_host_plan.c): one group per wavefront only */
+			if (k2a_pkcfg_G[cfg] != 64 || (k2a_pkcfg_C[cfg] != 8 && k2a_pkcfg_C[cfg] != 16)) { snprintf(g_err, sizeof(g_err), "bad pair-maximum class"); return -1; }
+			fn = (qd ? g_fill_pkq_defer_pm : g_fill_pk_defer_pm)[k2a_pkcfg_C[cfg] == 16 ? 1 : 0][rebased ? 1 : 0];
+			fn2 = g_argmax_pm[k2a_pkcfg_C[cfg] == 16 ? 1 : 0][rebased ? 1 : 0];
+		}
+#else
+		if (sc->pk_pm != 0) { snprintf(g_err, sizeof(g_err), "pair-maximum class in a build without the form"); return -1; }
+#endif
 		hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * K2A_WPB), 0, (hipStream_t)stream, *sc, pairs, order2, ntasks, seq, tb, res, qd);
 		CHECK(hipGetLastError());
-		hipLaunchKernelGGL(g_argmax[cfg][rebased ? 1 : 0], dim3((3 * ntasks + 64 * K2A_WPB - 1) / (64 * K2A_WPB)), dim3(64 * K2A_WPB), 0, (hipStream_t)stream,
+		hipLaunchKernelGGL(fn2, dim3((3 * ntasks + 64 * K2A_WPB - 1) / (64 * K2A_WPB)), dim3(64 * K2A_WPB), 0, (hipStream_t)stream,
 		                   *sc, pairs, order2, ntasks, seq, tb, res, (const K2aQueueDesc*)qd);
 		CHECK(hipGetLastError());
 		/* third pass: one group of 16 lanes per frozen book; the grid covers every alignment of the class, wavefronts beyond the

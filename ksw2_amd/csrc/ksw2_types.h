@@ -61,6 +61,14 @@
 #define K2A_FOLD_AFTER 1
 #endif
 #define K2A_CK_REC_WORDS(C) (2 * (C))
+/* "Pair maximum" form of those fills (ksw2_lane_pk.h, K2aLanePk PM): one running maximum per PAIR of rows instead of one per row, a
+ * record's first C / 2 dwords hold them (the record keeps its size), and the second pass resolves the row.  1 = classes that
+ * qualify take it (ksw2_host_plan.c, K2aScoring.pk_pm); 0 = no class does: the per-row form everywhere, for A/B libraries.  It
+ * needs the open form (the pair's second row is read out of its F register, which sits H - q - e behind) and the fold behind the loop. */
+#ifndef K2A_PAIR_MAX
+#define K2A_PAIR_MAX 1
+#endif
+#define K2A_PAIR_MAX_ON ((K2A_PAIR_MAX) && (K2A_HL_OPEN) && (K2A_FOLD_AFTER))
 #define K2A_CK_BLOCK_BYTES(steps, NG, hs, C) \
 	((size_t)(steps) * 512 + (size_t)(NG) * (hs) * 16 + ((K2A_FOLD_AFTER) && (NG) == 1 ? (size_t)(hs) * K2A_CK_REC_WORDS(C) * 4 : (size_t)0))
 #define K2A_PK_NIBBLES(C, dual) (!(dual) && (C) == 16)
@@ -92,6 +100,11 @@ typedef struct K2aScoring {
 	 * build of every packed body, whose wavefront-uniform slow path adds it to the candidates (K2aLanePk::step_rows); the device's plain
 	 * build never looks at it (host builds: K2A_TN_PATH, ksw2_lane_pk.h).  pk_tnc: what a TARGET wildcard row (pk_tn1 != 0; profile byte 0) adds instead of a byte: q + e + sN - pk_base */
 	int32_t pk_base, pk_tnc;
+	/* deferred one-group classes in the pair-maximum form (K2A_PAIR_MAX): the slack of the fold's freeze test, delta + q > 0 -- delta =
+	 * max(smax + q + e, -smin, q + e) bounds the difference of two adjacent rows' maxima, q what a border value may add to a pair's
+	 * maximum (ksw2_lane_pkfold.h, k2a_pkfold_task_pm).  0: the per-row form.  Set per class by the host; the shim picks the fill's
+	 * instantiation and the second pass's behaviour by it; host builds of the lane code ignore it. */
+	int32_t pk_pm;
 } K2aScoring;
 
 /* register window classes of the diagonal-major kernel: K slots of 64 target positions hold diagonals of up to
