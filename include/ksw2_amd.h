@@ -464,8 +464,8 @@ int ksw2amd_sg(void *q, int tlen, const uint8_t *target, int gapo, int gape, int
  * intervals come back once for the CIGAR stage; on a failure every aln[] entry holds score 0, coordinates -1, n_cigar 0).
  * ksw2amd_sg_align: one pair on a ksw_ll_qinit profile; returns the score; on a failure 0 with those reset values, reported like
  * ksw_ll_i16.  Device failures: a negative code, no CPU fallback.
- * Free query ends: ksw2amd_ov_batch further below, score and end cell only -- the start cell and CIGAR of that mode are not computed yet,
- * nor is a suboptimal score (the two-piece gap cost: ksw2amd_sgd_align_batch below). */
+ * Free query ends: ksw2amd_ov_batch and ksw2amd_ov_align_batch further below.  Not computed: a suboptimal score (the two-piece gap cost:
+ * ksw2amd_sgd_align_batch below). */
 int ksw2amd_sg_align_batch(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
                            const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
 int ksw2amd_sg_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n,
@@ -525,7 +525,7 @@ int ksw2amd_sgd_align(void *km, void *q, int tlen, const uint8_t *target, int ga
  * Scoring arguments, ranges, residue codes, the 0x3fffffff rejection, flat chunking, the on-device code check, the reset values, on_device
  * arenas and error reporting are exactly those of ksw2amd_sg_batch / ksw2amd_sgd_batch; no CPU fallback.  ksw2amd_ov / ksw2amd_ovd: one pair on
  * a ksw_ll_qinit profile, failures reported like ksw_ll_i16.
- * Not computed yet: the start cell and a CIGAR of this mode, a suboptimal score. */
+ * The start cell and a CIGAR of this mode: ksw2amd_ov_align_batch below.  Not computed: a suboptimal score. */
 #define KSW2AMD_OV_QBEG 1   /* the query's start is free: a query prefix may stay unaligned at no cost */
 #define KSW2AMD_OV_QEND 2   /* the query's end is free:   a query suffix may stay unaligned at no cost */
 int ksw2amd_ov_batch      (int m, const int8_t *mat, int gapo, int gape, int ends, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
@@ -534,6 +534,42 @@ int ksw2amd_ov            (void *q, int tlen, const uint8_t *target, int gapo, i
 int ksw2amd_ovd_batch     (int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res);
 int ksw2amd_ovd_batch_flat(int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int n, const ksw2amd_lflat_t *in,    ksw2amd_lres_t *res);
 int ksw2amd_ovd           (void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int ends, int *qe, int *te);
+
+/* Overlap alignment with the start cell and a CIGAR (new): the ov / ovd entries above as one call in
+ * the three stages of ksw2amd_sg_align_batch -- the forward pass, the anchored start pass on the device from what the forward pass left there,
+ * the CIGAR stage.  The argument lists are those of the sg_align / sgd_align entries with `ends` placed as in ksw2amd_ov_batch.
+ * score, qe, te: bit for bit what ksw2amd_ov_batch / ksw2amd_ovd_batch return for the same `ends`.
+ * tb, qb: let G(tb, qb) be the global score of query[qb..qe] against target[tb..te] under the scalar ksw_extz (ksw_extd for the ovd entries)
+ *   with w = -1, zdrop = -1; G = -cost(qe - qb + 1) when the target interval is empty (tb = te + 1), -cost(te - tb + 1) when the query interval
+ *   is empty (qb = qe + 1).  The candidate start cells are (tb, 0), 0 <= tb <= te + 1, and with ends & KSW2AMD_OV_QBEG also (0, qb),
+ *   0 <= qb <= qe + 1.  score equals the largest G over the candidates (the identity stated above in the reference's terms), and (tb, qb) is
+ *   the candidate with G == score that has the LARGEST tb, then the LARGEST qb -- the tie rule of ksw2amd_ll_align_batch.  So: the empty target
+ *   interval (te + 1, 0) wins every tie, as in ksw2amd_sg_align_batch; a start inside the target (tb > 0, qb = 0) beats a start in row 0; within
+ *   row 0 the shortest query interval wins, the empty one (qb = qe + 1) before all others; the corner (0, 0) loses every tie.
+ *   qb is NOT qe - r.mte_q of the reference's reversed call: ksw_extz's left-aligned and score-only loops keep the LARGEST column on ties
+ *   (max > h ? max_j : j), these entries the smallest.
+ * ends == 0: every field of every result equals ksw2amd_sg_align_batch's (ksw2amd_sgd_align_batch's).
+ * Equal pieces: with (gapo2, gape2) = (gapo, gape), or with gapo2 >= gapo and gape2 >= gape, the ovd entries equal the ov entries in every field.
+ * CIGAR: both intervals non-empty -- exactly that of the scalar ksw_extz(km, qe-qb+1, query+qb, te-tb+1, target+tb, m, mat, gapo, gape, -1, -1,
+ *   KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR)), &ez) (ksw_extd with gapo2, gape2 for ovd), whose score equals `score`
+ *   (checked for every pair; a mismatch is reported as an error, never returned); empty target interval: the one operation (qe + 1) I; empty
+ *   query interval: the one operation (te + 1) D.
+ * flag: KSW_EZ_SCORE_ONLY (coordinates only, n_cigar = 0, no third stage), KSW_EZ_RIGHT, KSW_EZ_REV_CIGAR; any other bit, and any other bit of
+ *   ends, is KSW2AMD_E_PARAM, checked before anything is staged.
+ * Nothing is launched for qlen <= 0 -> score 0, the four coordinates -1, n_cigar 0; nor for tlen <= 0 with qlen > 0: without KSW2AMD_OV_QBEG
+ *   score -cost(qlen), qb 0, qe qlen - 1, te -1, tb 0, CIGAR qlen I (unless KSW_EZ_SCORE_ONLY); with it score 0, qb qlen, qe qlen - 1, te -1,
+ *   tb 0, n_cigar 0 -- the whole query hangs over the target.
+ * Range: as for ksw2amd_ov_batch / ksw2amd_ovd_batch, the 0x3fffffff rejection included; the ovd align entries take m 2..127 (the scalar
+ *   ksw_extd aligns nothing with m = 1), as ksw2amd_sgd_align_batch does.  aln == NULL with n > 0 is KSW2AMD_E_PARAM.
+ * The flat entries have the chunking, the on-device code check, the reset of every aln[] entry on a failure and the on_device behaviour of
+ * ksw2amd_sg_align_batch_flat (device arena: the span of [qoff + qb, qoff + qe] and [toff + tb, toff + te] comes back once for the CIGAR
+ * stage); the single-pair entries report failures like ksw_ll_i16.  No CPU fallback.  Not computed: a suboptimal score. */
+int ksw2amd_ov_align_batch      (void *km, int m, const int8_t *mat, int gapo, int gape, int ends, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+int ksw2amd_ov_align_batch_flat (void *km, int m, const int8_t *mat, int gapo, int gape, int ends, int flag, int n, const ksw2amd_lflat_t *in,    ksw2amd_laln_t *aln);
+int ksw2amd_ov_align            (void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int ends, int flag, ksw2amd_laln_t *aln);
+int ksw2amd_ovd_align_batch     (void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int flag, int n, const ksw2amd_lpair_t *pairs, ksw2amd_laln_t *aln);
+int ksw2amd_ovd_align_batch_flat(void *km, int m, const int8_t *mat, int gapo, int gape, int gapo2, int gape2, int ends, int flag, int n, const ksw2amd_lflat_t *in,    ksw2amd_laln_t *aln);
+int ksw2amd_ovd_align           (void *km, void *q, int tlen, const uint8_t *target, int gapo, int gape, int gapo2, int gape2, int ends, int flag, ksw2amd_laln_t *aln);
 
 /* The same in three phases, for callers that keep batches resident in HBM (and for benchmarking the
  * device part alone): create = pack + upload, run = kernels only (asynchronous on `stream`, a hipStream_t

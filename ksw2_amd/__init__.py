@@ -118,7 +118,9 @@ EXPORTS = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz
            "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
            "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
            "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align",
-           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd"]
+           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd",
+           "ksw2amd_ov_align_batch", "ksw2amd_ov_align_batch_flat", "ksw2amd_ov_align",
+           "ksw2amd_ovd_align_batch", "ksw2amd_ovd_align_batch_flat", "ksw2amd_ovd_align"]
 # entry points whose behaviour depends on KSW2AMD_* switches: the library reads its environment once per process, so this binding
 # re-reads it in front of each of them (tests and A/B scripts flip switches inside one process)
 _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw_extz", "ksw_extd", "ksw_gg", "ksw_extz2_sse41",
@@ -134,7 +136,9 @@ _ENV_ENTRIES = ["ksw_extz2_sse", "ksw_extd2_sse", "ksw_gg2", "ksw_gg2_sse", "ksw
            "ksw2amd_sg_align_batch", "ksw2amd_sg_align_batch_flat", "ksw2amd_sg_align",
            "ksw2amd_sgd_batch", "ksw2amd_sgd_batch_flat", "ksw2amd_sgd",
            "ksw2amd_sgd_align_batch", "ksw2amd_sgd_align_batch_flat", "ksw2amd_sgd_align",
-           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd"]
+           "ksw2amd_ov_batch", "ksw2amd_ov_batch_flat", "ksw2amd_ov", "ksw2amd_ovd_batch", "ksw2amd_ovd_batch_flat", "ksw2amd_ovd",
+           "ksw2amd_ov_align_batch", "ksw2amd_ov_align_batch_flat", "ksw2amd_ov_align",
+           "ksw2amd_ovd_align_batch", "ksw2amd_ovd_align_batch_flat", "ksw2amd_ovd_align"]
 KSW2AMD_OV_QBEG, KSW2AMD_OV_QEND = 1, 2      # ov_batch / ovd_batch: the query's start / end is free
 ERROR_FN = ctypes.CFUNCTYPE(None, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
 KSW_EZ_SPLICE_FOR, KSW_EZ_SPLICE_REV, KSW_EZ_SPLICE_FLANK = 0x100, 0x200, 0x400
@@ -313,6 +317,13 @@ class Library:
             L.ksw2amd_ovd_batch.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalResult)]
             L.ksw2amd_ovd_batch_flat.argtypes = [_int, _i8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalResult)]
             L.ksw2amd_ovd.argtypes = [ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]
+        if hasattr(L, "ksw2amd_ov_align_batch"):    # (nor the overlap start pass's twin: tests/ova_util.py adds it)
+            L.ksw2amd_ov_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ov_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ov_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ovd_align_batch.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalPair), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ovd_align_batch_flat.argtypes = [km, _int, _i8p, _int, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalFlat), ctypes.POINTER(LocalAln)]
+            L.ksw2amd_ovd_align.argtypes = [km, ctypes.c_void_p, _int, _u8p, _int, _int, _int, _int, _int, _int, ctypes.POINTER(LocalAln)]
         for name in _ENV_ENTRIES:
             if hasattr(L, name):
                 setattr(L, name, with_env(getattr(L, name)))
@@ -929,6 +940,60 @@ class Library:
         finally:
             _libc.free(prof)
         return int(score), qe.value, te.value
+
+    # ---- overlap alignment with the start cell and a CIGAR
+    def ov_align_batch(self, queries, targets, mat, gapo, gape, ends, flag=0, m=None, pairs=None, n=None, aln=None, costs2=None):
+        """ksw2amd_ov_align_batch(km=NULL, ...) (costs2 = (gapo2, gape2): ksw2amd_ovd_align_batch): ov_batch plus the start cell and the CIGAR
+        -> list of dicts score, qb, qe, tb, te, n_cigar, cigar (query[qb..qe] against target[tb..te]; tb == te + 1: the empty target interval,
+        CIGAR (qe + 1) I; qb == qe + 1: the empty query interval, CIGAR (te + 1) D; flag: KSW_EZ_SCORE_ONLY / KSW_EZ_RIGHT /
+        KSW_EZ_REV_CIGAR).  aln: a LocalAln array that the caller keeps, as for ll_align_batch_flat."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        if pairs is None:
+            n = len(queries)
+            pairs, keep = self.local_pairs(queries, targets)
+        elif n is None:
+            raise ValueError("a prebuilt pair array needs its length n")
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        if costs2 is None:
+            rc = self.lib.ksw2amd_ov_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, ends, flag, n, pairs, aln)
+        else:
+            rc = self.lib.ksw2amd_ovd_align_batch(None, m, mat.ctypes.data_as(_i8p), gapo, gape, costs2[0], costs2[1], ends, flag, n, pairs, aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def ov_align_batch_flat(self, base, qoff, qlen, toff, tlen, mat, gapo, gape, ends, flag=0, m=None, device_base=None, aln=None, costs2=None):
+        """ksw2amd_ov_align_batch_flat(km=NULL, ...) (costs2: ksw2amd_ovd_align_batch_flat): ov_align_batch on an arena (see ll_batch_flat)
+        -> list of dicts."""
+        mat = np.ascontiguousarray(mat, dtype=np.int8)
+        m = int(round(len(mat) ** 0.5)) if m is None else m
+        f, n, keep = self._local_flat(base, qoff, qlen, toff, tlen, device_base)
+        own = aln is None
+        aln = (LocalAln * max(n, 1))() if own else aln
+        if costs2 is None:
+            rc = self.lib.ksw2amd_ov_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, ends, flag, n, ctypes.byref(f), aln)
+        else:
+            rc = self.lib.ksw2amd_ovd_align_batch_flat(None, m, mat.ctypes.data_as(_i8p), gapo, gape, costs2[0], costs2[1], ends, flag, n, ctypes.byref(f), aln)
+        out = [self._aln_to_dict(aln[i], free_cigar=own) for i in range(n)]
+        self._check(rc)
+        return out
+
+    def ov_align(self, query, target, mat, gapo, gape, ends, flag=0, m=None, size=2, costs2=None):
+        """ksw_ll_qinit(NULL, size, ...) + ksw2amd_ov_align(km=NULL, ...) (costs2: ksw2amd_ovd_align) -> dict like ov_align_batch's."""
+        prof, ta, tp, keep = self._lld_profile(query, target, mat, m, size)
+        try:
+            a = LocalAln()
+            if costs2 is None:
+                score = self.lib.ksw2amd_ov_align(None, prof, len(ta), tp, gapo, gape, ends, flag, ctypes.byref(a))
+            else:
+                score = self.lib.ksw2amd_ovd_align(None, prof, len(ta), tp, gapo, gape, costs2[0], costs2[1], ends, flag, ctypes.byref(a))
+        finally:
+            _libc.free(prof)
+        d = self._aln_to_dict(a)
+        assert d["score"] == int(score)
+        return d
 
     def sgd_align_batch(self, queries, targets, mat, gapo, gape, gapo2, gape2, flag=0, m=None, pairs=None, n=None, aln=None):
         """ksw2amd_sgd_align_batch(km=NULL, ...): sg_align_batch under the two-piece gap cost (the CIGAR is the scalar ksw_extd's) -> list of

@@ -333,7 +333,8 @@ typedef struct {
  * section 3.22): launch = k2a_shim_launch_sgd and rev = k2a_shim_launch_sgd_rev, which only ksw2_host_sgd.o names; the ll_dual_t's fwd is not
  * called and may be NULL.
  * ov (ksw2_host_ov.c): the overlap entries -- launch = k2a_shim_launch_ov (with an ll_dual_t: k2a_shim_launch_ovd), which
- * only ksw2_host_ov.o names; never with a rev.  ends (KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND, checked by ll_batch_ex / llf_batch_ex) travels to the
+ * only ksw2_host_ov.o names; with a rev (ksw2_host_ova.c): k2a_shim_launch_ov_rev / _ovd_rev, which only
+ * ksw2_host_ova.o names.  ends (KSW2AMD_OV_QBEG | KSW2AMD_OV_QEND, checked by ll_batch_ex / llf_batch_ex) travels to the
  * kernels in every task's pad, a pair with the query's end free is packed only if its columns fit the 16-bit index as well, a query without a
  * target scores 0 when its start is free, and the trace line says "ov" (two-piece: "ovd") and ends.  Every other entry sets ov = ends = 0 */
 typedef struct {
@@ -346,6 +347,8 @@ size_t ll_pair_bytes(int qlen, int tlen, int sub, int dual, int fit);
 int ll_sg_pk_admit(int qlen, int gapo, int gape, const ll_dual_t *du, int smax);      /* du: cost(qlen) of the two pieces */
 int ll_sg_check_range(int i, int qlen, int gapo, int gape, const ll_dual_t *du, int smax);
 int ll_ov_check_ends(const ll_fit_t *ft);
+void ov_mode(ll_fit_t *ft, int ends);      /* ksw2_host_ov.c: the overlap mode with its forward launch, for ksw2_host_ova.c as well */
+void ovd_mode(ll_fit_t *ft, ll_dual_t *du, int gapo2, int gape2, int ends);
 int ll_check_args(int m, const int8_t *mat, int gapo, int gape);
 int ll_bad_code(const uint8_t *s, int len, int m);
 int ll_batch_ex(int m, const int8_t *mat, int gapo, int gape, int n, const ksw2amd_lpair_t *pairs, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *begs,
@@ -363,7 +366,8 @@ int lla_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int fla
 int llf_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lflat_t *in, ksw2amd_laln_t *aln, ll_rev_fn rev,
                  const ll_dual_t *du);
 /* the stages of ksw2amd_sg_align_batch behind the two kernel passes (ksw2_host_sga.c), and the two batch entries with their launches
- * and the two-piece cost as parameters (ksw2_host_sgd.c) */
+ * and the two-piece cost as parameters (ksw2_host_sgd.c); with ft->ov the stages of ksw2amd_ov_align_batch (ksw2_host_ova.c): the cell check
+ * admits a start in row 0 when the query's start is free, and the CIGAR stage aligns query[qb..qe] */
 void sga_reset(int n, ksw2amd_laln_t *aln);
 int sga_check_flag(int flag);
 int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na);

@@ -136,7 +136,7 @@ static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const
 		const int ql = src_qlen(src, i), tl = src_tlen(src, i);
 		if (ql > 0 && tl <= 0) {                                 /* the whole query inserted before the target */
 			res[i].score = free_beg ? 0 : -(int)ll_sg_cost(ql, gapo, gape, du); res[i].qe = ql - 1; res[i].te = -1;
-			if (beg) { beg[i].score = res[i].score; beg[i].qb = 0; beg[i].tb = 0; }      /* (rev: the empty interval, tb = te + 1) */
+			if (beg) { beg[i].score = res[i].score; beg[i].qb = free_beg ? ql : 0; beg[i].tb = 0; }      /* (rev: the empty interval, tb = te + 1; free_beg: the whole query hangs over, qb = qe + 1) */
 		}
 	}
 }
@@ -163,9 +163,12 @@ static void ll_fit_corners(const ll_src_t *src, int n, int gapo, int gape, const
  * ft and du together (never with sb): ksw2amd_sgd_batch and, with rev, ksw2amd_sgd_align_batch (ksw2_host_sgd.c) --
  * the forward launch is ft->launch (du->fwd is not called), par.oe2 / ge2 and the 16-byte boundary come from du, the corners, the packed
  * admission and the range check use cost(qlen) = min of the two pieces; the trace lines say "sgd" / "sgda"
- * ft->ov (never with rev or sb; with and without du): ksw2amd_ov_batch / ksw2amd_ovd_batch (ksw2_host_ov.c) -- the
+ * ft->ov (never with sb; with and without du): ksw2amd_ov_batch / ksw2amd_ovd_batch (ksw2_host_ov.c) -- the
  * semi-global chunk with ft->ends in every task's pad; a pair whose query end is free is packed only if qlen - 1 fits the packed form's
- * 16-bit column index as well, a query without a target scores 0 if its start is free; the trace line says "ov" / "ovd" and ends */
+ * 16-bit column index as well, a query without a target scores 0 if its start is free; the trace line says "ov" / "ovd" and ends
+ * ft->ov with rev: ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch (ksw2_host_ova.c) -- rev is the caller's anchored start
+ * pass of this mode; beg[i] = its score, qb, tb; its last-row maximum keeps a 16-bit column too, so a pair whose query start is free is packed
+ * under the same condition; the trace lines say "ova" / "ovda" */
 int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, const ll_src_t *src, ksw2amd_lres_t *res, ll_rev_fn rev, K2aLLBeg *beg,
              const ll_sub_t *sb, ksw2amd_lsub_t *sub, const ll_dual_t *du, const ll_fit_t *ft)
 {
@@ -173,8 +176,8 @@ int ll_chunk(int m, const int8_t *mat, int smax, int gapo, int gape, int n, cons
 	const int form = fv && *fv ? atoi(fv) : 1;        /* 0: int32 only; 1: packed for same-shape admissible pairs; 2: packed for every admissible pair */
 	const int lds = m > 5 || env_flag(lv, 0);
 	const ll_fwd_fn fwd = ft ? ft->launch : du ? du->fwd : k2a_shim_launch_ll;
-	const char *tn = ft && ft->ov ? (du ? "ovd" : "ov") : ft ? (du ? (rev ? "sgda" : "sgd") : rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
-	const int ov_end = ft && ft->ov && (ft->ends & KSW2AMD_OV_QEND);
+	const char *tn = ft && ft->ov ? (du ? (rev ? "ovda" : "ovd") : rev ? "ova" : "ov") : ft ? (du ? (rev ? "sgda" : "sgd") : rev ? "sga" : "sg") : du ? "lld" : "ll";      /* the trace lines' prefix */
+	const int ov_end = ft && ft->ov && ((ft->ends & KSW2AMD_OV_QEND) || (rev && (ft->ends & KSW2AMD_OV_QBEG)));      /* a packed last-row maximum: forward, or the start pass's */
 	char ovs[24] = "";
 	const ksw2amd_lflat_t *flat = src->flat;
 	ll_sort_t *pk = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (2 * (size_t)n + 2)), *i32 = (ll_sort_t*)malloc(sizeof(ll_sort_t) * (size_t)(n + 1));

@@ -8,16 +8,17 @@
  * ll_dual_t which second piece to score with.
  *
  * This is the only host object that refers to k2a_shim_launch_ov and k2a_shim_launch_ovd (the simulator builds of the other
- * tests/ *_util.py link the other host objects without them).
+ * tests/ *_util.py link the other host objects without them); ksw2_host_ova.c takes the mode from ov_mode / ovd_mode here.
  */
 #include "ksw2_host_int.h"
 
-static void ov_mode(ll_fit_t *ft, int ends)
+/* (shared with ksw2_host_ova.c, which must not name the two launches itself) */
+void ov_mode(ll_fit_t *ft, int ends)
 {
 	ft->launch = k2a_shim_launch_ov; ft->ov = 1; ft->ends = ends;
 }
 
-static void ovd_mode(ll_fit_t *ft, ll_dual_t *du, int gapo2, int gape2, int ends)
+void ovd_mode(ll_fit_t *ft, ll_dual_t *du, int gapo2, int gape2, int ends)
 {
 	ft->launch = k2a_shim_launch_ovd; ft->ov = 1; ft->ends = ends;
 	du->gapo2 = gapo2; du->gape2 = gape2; du->fwd = 0; du->pk_reg = 1;      /* the forward launch is ft->launch; every packed form is built */

@@ -13,6 +13,9 @@
  * This is the only host object that refers to k2a_shim_launch_sg_rev (it names k2a_shim_launch_sg too, like ksw2_host_sg.c).
  * The two-piece entries (ksw2_host_sgd.c) run the same three stages through sga_align_ex / sga_align_flat_ex with
  * their own two launches and an ll_dual_t: stage 3 is then the scalar-contract ksw_extd.
+ * The overlap entries (ksw2_host_ova.c) run them with ft->ov: the start pass may then name a start (0, qb) in row 0,
+ * which ova_cells admits, and stage 3 aligns query[qb..qe]; an empty query interval's CIGAR, (te + 1) D, is written here.  With qb = 0
+ * everything below is what it was.
  */
 #include "ksw2_host_int.h"
 
@@ -22,7 +25,8 @@ void sga_reset(int n, ksw2amd_laln_t *aln)
 	for (i = 0; aln && i < n; ++i) { aln[i].score = 0; aln[i].qb = aln[i].qe = aln[i].tb = aln[i].te = -1; aln[i].n_cigar = 0; }
 }
 
-static inline int sga_has_interval(const ksw2amd_laln_t *a) { return a->qe >= 0 && a->te >= 0 && a->tb <= a->te; }
+/* both intervals non-empty (qb > qe: the overlap entries' empty query interval; qb = 0 in the semi-global ones) */
+static inline int sga_has_interval(const ksw2amd_laln_t *a) { return a->qe >= 0 && a->te >= 0 && a->tb <= a->te && a->qb <= a->qe; }
 
 /* after stages 1 and 2: aln[i] = score, the query's ends and the interval, the start pass checked against the forward pass (no CIGAR
  * yet).  qlen / tlen: the pairs' lengths, `stride` ints apart.  Returns through *na the pairs with a non-empty interval */
@@ -48,9 +52,34 @@ int sga_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, co
 	return KSW2AMD_OK;
 }
 
-/* stage 3.  Empty intervals: qlen I, written here.  The na pairs with an interval: query x target[tb..te] as extension pairs into HOST
- * memory; the caller's CIGAR buffers travel through ez[] and back.  at_start = 0: pairs[i].target is the full target; 1: it already points
- * at residue tb (the intervals of a device arena, brought back).  pairs[i].query is the whole query either way.  du: the scalar ksw_extd
+/* the same for the overlap entries (ksw2amd_ov_align_batch): the start pass may name exactly the candidate cells --
+ * (tb, 0) with 0 <= tb <= te + 1, or, with the query's start free, (0, qb) with 0 <= qb <= qe + 1 -- with the forward pass's score */
+static int ova_cells(int n, const int32_t *qlen, const int32_t *tlen, size_t stride, int ends, const ksw2amd_lres_t *res, const K2aLLBeg *beg, ksw2amd_laln_t *aln, int *na_)
+{
+	int i, na = 0;
+	char msg[128];
+	for (i = 0; i < n; ++i) {
+		ksw2amd_laln_t *a = &aln[i];
+		const int ql = qlen[i * stride], tl = tlen[i * stride];
+		a->score = res[i].score; a->qe = res[i].qe; a->te = res[i].te; a->qb = beg[i].qb; a->tb = beg[i].tb;
+		a->n_cigar = 0;
+		if (ql <= 0) { a->score = 0; a->qb = a->qe = a->tb = a->te = -1; continue; }
+		if (tl <= 0) { a->qb = (ends & KSW2AMD_OV_QBEG) ? ql : 0; a->tb = 0; continue; }      /* te = -1: the query inserted, or all of it hanging over */
+		if (beg[i].score != res[i].score
+		    || !((beg[i].qb == 0 && beg[i].tb >= 0 && beg[i].tb <= res[i].te + 1)
+		         || ((ends & KSW2AMD_OV_QBEG) && beg[i].tb == 0 && beg[i].qb >= 0 && beg[i].qb <= res[i].qe + 1))) {
+			snprintf(msg, sizeof(msg), "%d: forward %d, reversed %d (qb %d, tb %d, qe %d, te %d)", i, res[i].score, beg[i].score, beg[i].qb, beg[i].tb, res[i].qe, res[i].te);
+			return fail(KSW2AMD_E_NODEVICE, "overlap alignment: internal error, start pass disagrees with the forward pass on pair %s", msg);
+		}
+		na += sga_has_interval(a);
+	}
+	*na_ = na;
+	return KSW2AMD_OK;
+}
+
+/* stage 3.  Empty intervals: (qe + 1) I for an empty target interval, (te + 1) D for an empty query interval (overlap entries), written here.  The na pairs with an interval: query x target[tb..te] as extension pairs into HOST
+ * memory; the caller's CIGAR buffers travel through ez[] and back.  at_start = 0: pairs[i].query / target are the full sequences; 1: they already point
+ * at residues qb / tb (the intervals of a device arena, brought back).  qb = 0 in the semi-global entries.  du: the scalar ksw_extd
  * with (gapo2, gape2), the pieces in the caller's order, instead of ksw_extz */
 int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag, int n, const ksw2amd_lpair_t *pairs, int at_start, int na, ksw2amd_laln_t *aln,
                const ll_dual_t *du)
@@ -63,12 +92,12 @@ int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag,
 	for (i = 0; i < n; ++i) {
 		ksw2amd_laln_t *a = &aln[i];
 		ksw_extz_t z;
-		if (a->qe < 0 || sga_has_interval(a)) continue;
+		if (a->qe < 0 || sga_has_interval(a) || (a->qb > a->qe && a->te < 0)) continue;      /* (the last: all of the query hangs over no target) */
 		z.cigar = a->cigar; z.m_cigar = a->m_cigar;
 		ez_reserve(km, &z, 1);
 		a->cigar = z.cigar; a->m_cigar = z.m_cigar;
 		if (!a->cigar) { a->m_cigar = 0; return fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); }
-		a->cigar[0] = (uint32_t)(a->qe + 1) << 4 | 1u;
+		a->cigar[0] = a->qb > a->qe ? (uint32_t)(a->te + 1) << 4 | 2u : (uint32_t)(a->qe + 1) << 4 | 1u;
 		a->n_cigar = 1;
 	}
 	if (na == 0) return KSW2AMD_OK;
@@ -79,7 +108,7 @@ int sga_cigars(void *km, int m, const int8_t *mat, int gapo, int gape, int flag,
 	for (i = 0, k = 0; i < n; ++i) {
 		const ksw2amd_laln_t *a = &aln[i];
 		if (!sga_has_interval(a)) continue;
-		pp[k].query = pairs[i].query; pp[k].qlen = a->qe + 1;
+		pp[k].query = pairs[i].query + (at_start ? 0 : a->qb); pp[k].qlen = a->qe - a->qb + 1;
 		pp[k].target = pairs[i].target + (at_start ? 0 : a->tb); pp[k].tlen = a->te - a->tb + 1;
 		pp[k].w = -1; pp[k].zdrop = -1; pp[k].end_bonus = 0;
 		pp[k].flag = KSW_EZ_GENERIC_SC | (flag & (KSW_EZ_RIGHT | KSW_EZ_REV_CIGAR));
@@ -129,7 +158,8 @@ int sga_align_ex(void *km, int m, const int8_t *mat, int gapo, int gape, int fla
 	}
 	if ((rc = ll_batch_ex(m, mat, gapo, gape, n, pairs, res, rev, beg, 0, 0, du, ft)) != KSW2AMD_OK) goto out;
 	if (n == 0) goto out;
-	if ((rc = sga_cells(n, &pairs[0].qlen, &pairs[0].tlen, sizeof(pairs[0]) / sizeof(int32_t), res, beg, aln, &na)) != KSW2AMD_OK) goto out;
+	if ((rc = ft->ov ? ova_cells(n, &pairs[0].qlen, &pairs[0].tlen, sizeof(pairs[0]) / sizeof(int32_t), ft->ends, res, beg, aln, &na)
+	                 : sga_cells(n, &pairs[0].qlen, &pairs[0].tlen, sizeof(pairs[0]) / sizeof(int32_t), res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if (flag & KSW_EZ_SCORE_ONLY) goto out;
 	rc = sga_cigars(km, m, mat, gapo, gape, flag, n, pairs, 0, na, aln, du);
 out:
@@ -164,9 +194,9 @@ int sga_align_flat_ex(void *km, int m, const int8_t *mat, int gapo, int gape, in
 	/* stages 1 and 2 on the borrowed arena */
 	if ((rc = llf_batch_ex(m, mat, gapo, gape, n, in, res, rev, beg, 0, 0, du, ft)) != KSW2AMD_OK) goto out;
 	if (n == 0) goto out;
-	if ((rc = sga_cells(n, in->qlen, in->tlen, 1, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
+	if ((rc = ft->ov ? ova_cells(n, in->qlen, in->tlen, 1, ft->ends, res, beg, aln, &na) : sga_cells(n, in->qlen, in->tlen, 1, res, beg, aln, &na)) != KSW2AMD_OK) goto out;
 	if (flag & KSW_EZ_SCORE_ONLY) goto out;
-	/* stage 3: the whole query x [toff + tb, toff + te] under the scalar ksw_extz (du: ksw_extd) contract.  Host arena: pointers into it.  Device arena: the
+	/* stage 3: [qoff + qb, qoff + qe] (semi-global: the whole query) x [toff + tb, toff + te] under the scalar ksw_extz (du: ksw_extd) contract.  Host arena: pointers into it.  Device arena: the
 	 * span of the aligned intervals and their queries comes back in one copy, then the same pointer path */
 	pp = (ksw2amd_lpair_t*)malloc(sizeof(*pp) * (size_t)n);
 	if (!pp) { rc = fail(KSW2AMD_E_NOMEM, "semi-global alignment: host allocation failed%s", ""); goto out; }
@@ -176,7 +206,7 @@ int sga_align_flat_ex(void *km, int m, const int8_t *mat, int gapo, int gape, in
 		for (i = 0; i < n; ++i) {
 			const ksw2amd_laln_t *a = &aln[i];
 			if (!sga_has_interval(a)) continue;
-			if (in->qoff[i] < lo) lo = in->qoff[i];
+			if (in->qoff[i] + (uint64_t)a->qb < lo) lo = in->qoff[i] + (uint64_t)a->qb;
 			if (in->toff[i] + (uint64_t)a->tb < lo) lo = in->toff[i] + (uint64_t)a->tb;
 			if (in->qoff[i] + (uint64_t)a->qe + 1 > hi) hi = in->qoff[i] + (uint64_t)a->qe + 1;
 			if (in->toff[i] + (uint64_t)a->te + 1 > hi) hi = in->toff[i] + (uint64_t)a->te + 1;
@@ -188,7 +218,7 @@ int sga_align_flat_ex(void *km, int m, const int8_t *mat, int gapo, int gape, in
 			const ksw2amd_laln_t *a = &aln[i];
 			pp[i].query = pp[i].target = 0; pp[i].qlen = in->qlen[i]; pp[i].tlen = in->tlen[i];
 			if (!sga_has_interval(a)) continue;
-			pp[i].query = host + (in->qoff[i] - lo); pp[i].target = host + (in->toff[i] + (uint64_t)a->tb - lo);
+			pp[i].query = host + (in->qoff[i] + (uint64_t)a->qb - lo); pp[i].target = host + (in->toff[i] + (uint64_t)a->tb - lo);
 		}
 	} else
 		for (i = 0; i < n; ++i) {                 /* (a device arena without an interval: the pointers are never followed) */

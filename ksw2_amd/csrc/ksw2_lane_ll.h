@@ -117,7 +117,7 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * (DESIGN.md section 3.22).  cost(l) = min(gapo + l * gape, gapo2 + l * gape2), the pieces as the caller orders them; B = cost(ncols), row -1
  * is B - cost(j + 1) with E' and E2' opened from it, column -1 of the reverse pass is max(B - cost(i + 1), 0), and F2' of column 0 is opened
  * from column -1 like F'.  cost() is non-decreasing, so cost(j + 1) <= B and the arguments above carry over; step() is DUAL's as it stands. */
-/* OV (with FIT, with and without DUAL, never with REV): the overlap mode of ksw2amd_ov_batch / ksw2amd_ovd_batch --
+/* OV (with FIT, with and without DUAL; with REV: below): the overlap mode of ksw2amd_ov_batch / ksw2amd_ovd_batch --
  * FIT with free query ends, chosen per task by `ends` (K2aLLTask.pad: bit 0 the query's start, bit 1 its end; wavefront-uniform).
  * Bit 0: row -1 is H(-1, j) = 0, i.e. H' = B in every column with E' = sat(B - oe) (and E2') opened from it, in place of fit_top's ramp.
  * Every true H(t, j) is still >= -cost(j + 1) >= -B (start in column -1 of row t, insert the query up to j), so the bias and the clamped gap
@@ -126,7 +126,16 @@ typedef uint32_t k2a_ll_v4 __attribute__((vector_size(16)));
  * clast = (nrows - 1) % C -- the same register in every lane, so in that generation every lane folds hl[clast] after each step into one
  * running (maximum, first column) per half (strict >, columns ascending; packed: the row-maximum idiom of the local step, 16-bit column),
  * and in gen_end the lane that owns row nrows - 1 folds (maximum, nrows - 1, column) into its key beside the last column.  The fold starts
- * at (0, column 0), which is never above the real cell of column 0 (H' >= 0) and equals it when that cell is 0. */
+ * at (0, column 0), which is never above the real cell of column 0 (H' >= 0) and equals it when that cell is 0.
+ * OV with REV: the start pass of ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch -- FIT with REV over the reversed
+ * prefix that ends in the forward pass's cell (te, qe): rl = te + 1 and cl = qe + 1 per half, and qe may lie before the last column.  B stays
+ * cost(bcols) of the forward task's columns, so row -1 (always fit_top's ramp here, whatever bit 0 says) and fit_left are taken from bcols and
+ * not from the rectangle.  Packed: a half stops changing hl[] once jj has left its own columns (cmask), so hl[] holds the half's last column
+ * cl[h] - 1 when the lane has walked the task's.  The key starts at row -1 of that column, (B - cost(cl[h]), -1, cl[h] - 1).  Bit 0 (the free
+ * query start of the forward pass) makes the rectangle's last row a candidate row: in the generation that holds row rl[h] - 1 every lane folds
+ * strip register clr[h] = (rl[h] - 1) % C of half h as the forward pass folds clast -- generation and register may differ between the halves --
+ * and in gen_end its owner folds column -1, max(B - cost(rl[h]), 0), then (maximum, first column) into the key: smallest row, then smallest
+ * column, so the last row loses to every other row of the last column and wins over the corner (rl - 1, cl - 1). */
 template<bool PK, bool LDSP, bool REV = false, bool SUB = false, bool DUAL = false, bool FIT = false, bool OV = false>
 struct K2aLaneLL {
 	enum { C = K2A_LL_C, NH = PK ? 2 : 1 };
@@ -141,6 +150,7 @@ struct K2aLaneLL {
 	                                                     * half), pw: code 4; LDS profile: pa / pb = row code * m */
 	int ends, clast;                           /* OV: the task's free query ends; the last row's strip register in the last generation, else -1 */
 	uint32_t lmax, lcol;                       /* OV: the last row's largest H' so far and its first column */
+	int bcols, clr[OV && REV ? NH : 1];        /* OV with REV: the columns B was taken from; the last row's strip register per half in its generation, else -1 */
 	K2aLLKey key[NH];
 	int rl[REV ? NH : 1], cl[REV ? NH : 1];    /* REV: rows / columns of each half's prefix rectangle (0: the half scored 0) */
 
@@ -151,6 +161,9 @@ struct K2aLaneLL {
 		for (int h = 0; h < (REV ? NH : 1); ++h) {
 			rl[h] = rl_[h]; cl[h] = cl_[h];
 			nrows = k2a_max(nrows, rl[h]); ncols = k2a_max(ncols, cl[h]);
+			if (OV && REV) {                       /* row -1 of the half's last column: the empty target interval */
+				key[h].s = fit_bias() - ov_cost(cl[h]); key[h].te = -1; key[h].qe = cl[h] - 1;
+			}
 		}
 	}
 
@@ -167,14 +180,15 @@ struct K2aLaneLL {
 			if (!REV) for (int h = 0; h < NH; ++h) key[h].s = -1;      /* REV: (0, -1), row -1 of the last column */
 		}
 		if (OV) { ends = tk.pad; clast = -1; lmax = lcol = 0; }
+		if (OV && REV) { bcols = ncols; for (int h = 0; h < NH; ++h) clr[OV && REV ? h : 0] = -1; }
 	}
 
 	/* FIT: B, and row -1 of column k for lane 0 of the first generation: H'(-1, k) and E'(0, k) = sat(H'(-1, k) - oe) */
 	K2A_FN int fit_bias() const { return (int)(bias & (PK ? 0xffffu : 0xffffffffu)); }
 	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e) const
 	{
-		if (OV && (ends & 1)) { h = bias; e = PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0); return; }      /* H(-1, k) = 0 */
-		const int v = (ncols - 1 - k) * (int)(ge & (PK ? 0xffffu : 0xffffffffu)), w = k2a_max(v - (int)(oe & (PK ? 0xffffu : 0xffffffffu)), 0);
+		if (OV && !REV && (ends & 1)) { h = bias; e = PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0); return; }      /* H(-1, k) = 0 */
+		const int v = ((OV && REV ? bcols : ncols) - 1 - k) * (int)(ge & (PK ? 0xffffu : 0xffffffffu)), w = k2a_max(v - (int)(oe & (PK ? 0xffffu : 0xffffffffu)), 0);
 		h = (uint32_t)v * (PK ? 0x10001u : 1u); e = (uint32_t)w * (PK ? 0x10001u : 1u);
 	}
 
@@ -188,7 +202,7 @@ struct K2aLaneLL {
 	K2A_FN void fit_top(int k, uint32_t &h, uint32_t &e, uint32_t &e2) const
 	{
 		const uint32_t mk = PK ? 0xffffu : 0xffffffffu;
-		if (OV && (ends & 1)) {
+		if (OV && !REV && (ends & 1)) {
 			h = bias; e = PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);
 			e2 = PK ? k2a_ll_subs(bias, oe2) : (uint32_t)k2a_max((int)bias - (int)oe2, 0);
 			return;
@@ -201,14 +215,38 @@ struct K2aLaneLL {
 	K2A_FN uint32_t fit_left(int i) const
 	{
 		if (DUAL) return i < 0 ? bias : (uint32_t)k2a_max(fit_bias() - fit_cost(i + 1), 0) * (PK ? 0x10001u : 1u);
-		return i < 0 ? bias : (uint32_t)(k2a_max(ncols - 1 - i, 0) * (int)(ge & (PK ? 0xffffu : 0xffffffffu))) * (PK ? 0x10001u : 1u);
+		return i < 0 ? bias : (uint32_t)(k2a_max((OV && REV ? bcols : ncols) - 1 - i, 0) * (int)(ge & (PK ? 0xffffu : 0xffffffffu))) * (PK ? 0x10001u : 1u);
+	}
+
+	/* OV with REV: cost(l), l >= 1, under the entry's one or two pieces */
+	K2A_FN int ov_cost(int l) const
+	{
+		const uint32_t mk = PK ? 0xffffu : 0xffffffffu;
+		return DUAL ? fit_cost(l) : (int)(oe & mk) + (l - 1) * (int)(ge & mk);
+	}
+	/* ... and strip register c of hl[], c wavefront-uniform: no indexed register access */
+	K2A_FN uint32_t ov_pick(int c) const
+	{
+		uint32_t v = hl[0];
+		switch (c) {
+#define K2A_LL_OVSEL(c) case c: v = hl[c]; break;
+		K2A_LL_OVSEL(1) K2A_LL_OVSEL(2) K2A_LL_OVSEL(3) K2A_LL_OVSEL(4) K2A_LL_OVSEL(5) K2A_LL_OVSEL(6) K2A_LL_OVSEL(7) K2A_LL_OVSEL(8)
+		K2A_LL_OVSEL(9) K2A_LL_OVSEL(10) K2A_LL_OVSEL(11) K2A_LL_OVSEL(12) K2A_LL_OVSEL(13) K2A_LL_OVSEL(14) K2A_LL_OVSEL(15)
+#undef K2A_LL_OVSEL
+		default: break;
+		}
+		return v;
 	}
 
 	/* start generation g: this lane's rows, their profile, zeroed columns (tab = the task's pen table in LDS, [row code * m + column code]) */
 	K2A_FN void gen_begin(int g, const uint8_t *r0, const uint8_t *r1, const uint8_t *tab)
 	{
 		i0 = g * K2A_LL_ROWS + lane * C;
-		if (OV) { clast = ((ends & 2) && (g + 1) * K2A_LL_ROWS >= nrows) ? (nrows - 1) % C : -1; lmax = lcol = 0; }
+		if (OV && !REV) { clast = ((ends & 2) && (g + 1) * K2A_LL_ROWS >= nrows) ? (nrows - 1) % C : -1; lmax = lcol = 0; }
+		if (OV && REV) {                           /* the halves' last rows: this generation's or not, per half */
+			lmax = lcol = 0;
+			for (int h = 0; h < NH; ++h) clr[OV && REV ? h : 0] = ((ends & 1) && rl[REV ? h : 0] > 0 && (rl[REV ? h : 0] - 1) / K2A_LL_ROWS == g) ? (rl[REV ? h : 0] - 1) % C : -1;
+		}
 		hu_prev = !FIT ? 0u : REV ? fit_left(i0 - 1) : bias;
 		const uint32_t f0 = !FIT ? 0u : PK ? k2a_ll_subs(bias, oe) : (uint32_t)k2a_max((int)bias - (int)oe, 0);      /* FIT: F'(i, 0) = sat(B - oe) */
 #pragma unroll
@@ -305,12 +343,23 @@ struct K2aLaneLL {
 				if (!FIT && hi > (int)rmax[c]) { rmax[c] = h; rcol[c] = jj2; }
 			}
 			hd = hl[c];
-			hl[c] = h;
+			hl[c] = (OV && REV && PK) ? (h & cmask) | (hl[c] & ~cmask) : h;      /* OV with REV: a half past its own last column keeps it */
 		}
 		hout = hl[C - 1];
 		eout = e;
 		e2out = e2;
-		if (OV && clast >= 0) {                    /* the last generation of a task with a free query end: one row's running maximum */
+		if (OV && REV) {
+			if (clr[0] >= 0 || clr[OV && REV ? NH - 1 : 0] >= 0) {      /* a generation that holds a half's last row, the query's start free */
+				uint32_t v = ov_pick(clr[0]);
+				if (PK) {
+					v = (clr[0] >= 0 ? v & 0xffffu : 0u) | (clr[OV && REV ? NH - 1 : 0] >= 0 ? ov_pick(clr[OV && REV ? NH - 1 : 0]) & 0xffff0000u : 0u);
+					const uint32_t d = k2a_ll_subs(v, lmax);
+					const uint32_t mask = k2a_ll_mul(k2a_ll_min(d, 0x10001u), 0xffffffffu);
+					lmax = k2a_ll_max(lmax, v);
+					lcol = (jj2 & mask) | (lcol & ~mask);
+				} else if ((int)v > (int)lmax) { lmax = v; lcol = jj2; }
+			}
+		} else if (OV && clast >= 0) {                    /* the last generation of a task with a free query end: one row's running maximum */
 			uint32_t v = hl[0];
 			switch (clast) {                       /* wavefront-uniform: no indexed register access */
 #define K2A_LL_OVSEL(c) case c: v = hl[c]; break;
@@ -339,7 +388,7 @@ struct K2aLaneLL {
 			for (int h = 0; h < NH; ++h) {
 				const uint32_t rm = FIT ? hl[c] : rmax[c];                            /* FIT: H'(i, ncols - 1), the row's last column */
 				const int s = (int)(PK ? (rm >> (16 * h)) & 0xffffu : rm);
-				const int j = FIT ? ncols - 1 : (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
+				const int j = (OV && REV) ? cl[REV ? h : 0] - 1 : FIT ? ncols - 1 : (int)(PK ? (rcol[c] >> (16 * h)) & 0xffffu : rcol[c]);
 				const int te = swapped ? j : i, qe = swapped ? i : j;
 				const bool take = i < (REV ? rl[REV ? h : 0] : nrows) && (FIT || s > 0) && k2a_ll_better(s, te, qe, key[h]);
 				key[h].s = take ? s : key[h].s;
@@ -347,7 +396,23 @@ struct K2aLaneLL {
 				key[h].qe = take ? qe : key[h].qe;
 			}
 		}
-		if (OV && clast >= 0 && (unsigned)(nrows - 1 - i0) < (unsigned)C) {      /* this lane owns the last row: its best cell, beside the last column's */
+		if (OV && REV) {                           /* the owner of a half's last row: column -1, then the row's best cell, beside the last column's */
+#pragma unroll
+			for (int h = 0; h < NH; ++h) {
+				const int lr = rl[REV ? h : 0] - 1;
+				const bool own = clr[OV && REV ? h : 0] >= 0 && (unsigned)(lr - i0) < (unsigned)C;
+				const int s0 = (int)(PK ? fit_left(lr) & 0xffffu : fit_left(lr));
+				const int s = (int)(PK ? (lmax >> (16 * h)) & 0xffffu : lmax), j = (int)(PK ? (lcol >> (16 * h)) & 0xffffu : lcol);
+				const bool take0 = own && k2a_ll_better(s0, lr, -1, key[h]);
+				key[h].s = take0 ? s0 : key[h].s;
+				key[h].te = take0 ? lr : key[h].te;
+				key[h].qe = take0 ? -1 : key[h].qe;
+				const bool take = own && k2a_ll_better(s, lr, j, key[h]);
+				key[h].s = take ? s : key[h].s;
+				key[h].te = take ? lr : key[h].te;
+				key[h].qe = take ? j : key[h].qe;
+			}
+		} else if (OV && clast >= 0 && (unsigned)(nrows - 1 - i0) < (unsigned)C) {      /* this lane owns the last row: its best cell, beside the last column's */
 #pragma unroll
 			for (int h = 0; h < NH; ++h) {
 				const int s = (int)(PK ? (lmax >> (16 * h)) & 0xffffu : lmax), j = (int)(PK ? (lcol >> (16 * h)) & 0xffffu : lcol);

@@ -236,6 +236,16 @@ int k2a_shim_launch_ov(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks
                        uint8_t *scratch, K2aLLRes *res, void *stream);
 int k2a_shim_launch_ovd(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
                         uint8_t *scratch, K2aLLRes *res, void *stream);
+/* The start pass of ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch, behind k2a_shim_launch_ov / k2a_shim_launch_ovd in
+ * the stream, on the same task table: half h reads res[slot] = (score, qe, te) and aligns reverse(columns[0 .. qe]) globally against
+ * reverse(rows[0 .. te]), anchored at (te, qe), free to end in any row of the last column and, with bit 0 of tasks[t].pad, in any column of
+ * the last row.  beg[slot] = (that pass's score, qb, tb): of the cells that reach the score the one with the largest tb, then the largest qb;
+ * tb = te + 1 the empty target interval, qb = qe + 1 the empty query interval.  A packed task holds a 16-bit column index: ncols <= 65536.
+ * Only ksw2_host_ova.c calls them (the other simulator builds have no such symbols). */
+int k2a_shim_launch_ov_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
+int k2a_shim_launch_ovd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2408,7 +2408,10 @@ k2a_extf_grp_kernel(const K2aExtf par, const K2aPair *__restrict__ pairs, const 
  * FIT with DUAL (k2a_sgd_kernel / k2a_sgd_rev_kernel): the same two passes under the two-piece gap cost -- DUAL's chain
  * and 16-byte boundary, FIT's bias and boundary values taken under cost(); lane 0 of the first generation gets E2' of row 0 from fit_top too.
  * OV (k2a_ov_kernel / k2a_ovd_kernel): FIT with the free query ends of tasks[t].pad -- fit_top's row -1 and, in the last
- * generation, the running maximum of the last target row; both live in K2aLaneLL<.., OV>, the schedule here is FIT's as it stands. */
+ * generation, the running maximum of the last target row; both live in K2aLaneLL<.., OV>, the schedule here is FIT's as it stands.
+ * OV with REV (k2a_ov_rev_kernel / k2a_ovd_rev_kernel): the start pass of ksw2amd_ov_align_batch.  Half h runs rows
+ * target[te_h - i] and columns query[qe_h - j], its own column limit cl = qe_h + 1; beg[tk.res[h]] = score of the pass, qe_h - (best column),
+ * te_h - (best row), the best column being -1 for the empty query interval. */
 template<bool PK, bool LDSP, bool REV, bool SUB = false, bool DUAL = false, bool FIT = false, bool OV = false>
 __device__ __forceinline__ void
 k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
@@ -2439,7 +2442,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 			const bool pos = FIT || r.score > 0;       /* FIT: a score may be <= 0, and every launched pair has its row te >= 0 */
 			fq[h] = r.qe; ft[h] = r.te;
 			rl[h] = pos ? (tk.swapped ? r.qe : r.te) + 1 : 0;
-			cl[h] = FIT ? tk.ncols : pos ? (tk.swapped ? r.te : r.qe) + 1 : 0;      /* FIT: the whole query */
+			cl[h] = (FIT && OV) ? k2a_max(r.qe + 1, 1) : FIT ? tk.ncols : pos ? (tk.swapped ? r.te : r.qe) + 1 : 0;      /* FIT: the whole query; OV: up to qe */
 			if (FIT) rl[h] = k2a_max(rl[h], 0);
 			rl[h] = k2a_min(rl[h], tk.nrows); cl[h] = k2a_min(cl[h], tk.ncols);      /* a forward cell always lies inside; never trust it for an address */
 		}
@@ -2511,7 +2514,7 @@ k2a_ll_task(const K2aLL &par, const K2aLLTask *__restrict__ tasks, int ntasks, c
 		}
 		if (lane == 0 && (h == 0 || tk.res[1] != tk.res[0])) {
 			if (REV && FIT) {                          /* k.te = -1: the empty interval, tb = te + 1 */
-				K2aLLBeg b; b.score = k.s - L.fit_bias(); b.qb = 0; b.tb = ft[h] - k.te;
+				K2aLLBeg b; b.score = k.s - L.fit_bias(); b.qb = OV ? fq[h] - k.qe : 0; b.tb = ft[h] - k.te;      /* OV: k.qe = -1 is the empty query interval */
 				beg[tk.res[h]] = b;
 			} else if (REV) {
 				const bool pos = k.s > 0;
@@ -2593,6 +2596,24 @@ k2a_ovd_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks,
                uint8_t *__restrict__ scratch, K2aLLRes *__restrict__ res)
 {
 	k2a_ll_task<PK, LDSP, false, false, true, true, true>(par, tasks, ntasks, seq, tab, scratch, res, nullptr, nullptr);
+}
+
+/* ... and where an overlap alignment starts (ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch): the anchored reverse
+ * pass behind k2a_ov_kernel / k2a_ovd_kernel, over the prefix rectangle that ends in (te, qe) */
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ov_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                  uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true, false, false, true, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
+}
+
+template<bool PK, bool LDSP>
+__global__ void __launch_bounds__(64 * K2A_WPB)
+k2a_ovd_rev_kernel(const K2aLL par, const K2aLLTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ tab,
+                   uint8_t *__restrict__ scratch, const K2aLLRes *__restrict__ fres, K2aLLBeg *__restrict__ beg)
+{
+	k2a_ll_task<PK, LDSP, true, false, true, true, true>(par, tasks, ntasks, seq, tab, scratch, nullptr, fres, beg);
 }
 
 /* two-piece gap cost (ksw2amd_lld_batch / ksw2amd_lld_align_batch): the forward pass and the start-cell pass.
@@ -3246,6 +3267,38 @@ int k2a_shim_launch_ovd(int pk, int lds, const K2aLL *par, const K2aLLTask *task
 	else if (pk) hipLaunchKernelGGL((k2a_ovd_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else if (lds) hipLaunchKernelGGL((k2a_ovd_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
 	else hipLaunchKernelGGL((k2a_ovd_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+/* start pass of ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch: the same grid over the same task table, behind k2a_shim_launch_ov /
+ * k2a_shim_launch_ovd in the stream.  All eight forms build without scratch */
+int k2a_shim_launch_ov_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                           uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "overlap alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ov_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (pk) hipLaunchKernelGGL((k2a_ov_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (lds) hipLaunchKernelGGL((k2a_ov_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_ov_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	CHECK(hipGetLastError());
+	return 0;
+}
+
+int k2a_shim_launch_ovd_rev(int pk, int lds, const K2aLL *par, const K2aLLTask *tasks, int ntasks, const uint8_t *seq, const uint8_t *tab,
+                            uint8_t *scratch, const K2aLLRes *res, K2aLLBeg *beg, void *stream)
+{
+	if (ntasks <= 0) return 0;
+	if (par->m < 1 || par->m > K2A_MAXM || (!lds && par->m > 5)) { snprintf(g_err, sizeof(g_err), "overlap alignment: bad profile form"); return -1; }
+	const dim3 grid((ntasks + K2A_WPB - 1) / K2A_WPB), block(64 * K2A_WPB);
+	const size_t lbytes = (size_t)2 * par->m * par->m;
+	if (pk && lds) hipLaunchKernelGGL((k2a_ovd_rev_kernel<true, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (pk) hipLaunchKernelGGL((k2a_ovd_rev_kernel<true, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else if (lds) hipLaunchKernelGGL((k2a_ovd_rev_kernel<false, true>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
+	else hipLaunchKernelGGL((k2a_ovd_rev_kernel<false, false>), grid, block, lbytes, (hipStream_t)stream, *par, tasks, ntasks, seq, tab, scratch, res, beg);
 	CHECK(hipGetLastError());
 	return 0;
 }

@@ -78,7 +78,17 @@ sgd_rev / sgd, and the batch-to-batch spread of k2a_lld_kernel.
 --ov: ksw2amd_ov_batch with both query ends free (overlap alignment) beside ksw2amd_ll_batch and ksw2amd_sg_batch on
 the pair array of --sg, the three ALTERNATING batch by batch in one process, library calls only in the clock; a parity sample against
 tests/ov_oracle.c.  --ktrace: per batch the time of k2a_ll_kernel, k2a_sg_kernel and k2a_ov_kernel, the ratios ov / ll and ov / sg, and the
-batch-to-batch spread of k2a_ll_kernel, which the gap between ov and ll is held against."""
+batch-to-batch spread of k2a_ll_kernel, which the gap between ov and ll is held against.
+
+  python tools/scripts/ll_bench.py --workload A --ov-align [--ktrace kernel_trace.csv] [--out profiles/ova_bench_A.json]
+
+--ov-align: ksw2amd_ov_align_batch / ksw2amd_ovd_align_batch with both query ends free on the pair array of --sg:
+ksw2amd_sg_align_batch and ksw2amd_sgd_align_batch with KSW_EZ_SCORE_ONLY (the start passes the new ones are held against, on the same pairs),
+ksw2amd_ov_align_batch and ksw2amd_ovd_align_batch with KSW_EZ_SCORE_ONLY, ksw2amd_ov_align_batch with CIGARs, and the by-hand pattern it
+replaces (ksw2amd_ov_batch, host reversal of both prefixes, ksw2amd_extz_batch for mqe / mte, the corner constants, ksw2amd_extz_batch for the
+CIGAR) alternate batch by batch, a warm-up plus --reps batches each, library calls only in the clock (the by-hand pattern's host work is
+reported beside it).  --ktrace: per batch the time of the four forward and the four start-pass kernels, the ratios ov_rev / sg_rev and
+ovd_rev / sgd_rev, and the batch-to-batch spread of each."""
 import argparse
 import ctypes
 import csv
@@ -573,6 +583,132 @@ def main_sg_align(a, lib, q, t, mat, gapo, gape, cells, form):
     return 0 if rec["parity_ok"] and rec["by_hand_agrees"] else 1
 
 
+def main_ov_align(a, lib, q, t, mat, gapo, gape, cells, form):
+    """--ov-align: the sg / sgd / ov / ovd align entries with SCORE_ONLY, ov_align with CIGARs and the by-hand pattern, alternating"""
+    from tests import ova_util as ova
+    swap = [len(x) > len(y) for x, y in zip(q, t)]
+    q, t = [y if w else x for x, y, w in zip(q, t, swap)], [x if w else y for x, y, w in zip(q, t, swap)]      # target >= query, as --sg
+    n = len(q)
+    L = lib.lib
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    mp = np.ascontiguousarray(mat, dtype=np.int8)
+    mpp = mp.ctypes.data_as(i8p)
+    pairs, keep = lib.local_pairs(q, t)                        # outside the clock
+    go2, ge2, ends = 24, 1, 3
+    names = ("sga_coords", "sgda_coords", "ova_coords", "ovda_coords", "ova_cigar")
+    alns = {k: (ksw2_amd.LocalAln * n)() for k in names}       # CIGAR buffers are reused from batch to batch
+    rp = lambda x, ty: x.ctypes.data_as(ctypes.POINTER(ty))
+    cost = lambda l: gapo + l * gape
+    hand = {}
+
+    def by_hand():
+        """ov_batch, host reversal of both prefixes, ksw2amd_extz_batch for mqe / mte, the two corner constants, ksw2amd_extz_batch for the
+        CIGAR; the time inside the three library calls and the host work between them are kept apart"""
+        r = np.zeros((n, 3), dtype=np.int32)
+        t0 = time.perf_counter()
+        rc = L.ksw2amd_ov_batch(5, mpp, gapo, gape, ends, n, pairs, rp(r, ksw2_amd.LocalResult))
+        t1 = time.perf_counter()
+        b1 = lib.make_batch([np.ascontiguousarray(x[qe::-1]) for x, qe in zip(q, r[:, 1])], [np.ascontiguousarray(y[te::-1]) for y, te in zip(t, r[:, 2])],
+                            mat, gapo, gape, w=-1, zdrop=-1, flag=SCORE_ONLY)
+        ez1 = (ksw2_amd.KswExtz * n)()
+        t2 = time.perf_counter()
+        rc |= L.ksw2amd_extz_batch(None, ctypes.byref(b1.sc), n, b1.pairs, ez1)
+        t3 = time.perf_counter()
+        st, sc = [], []
+        for i in range(n):                                     # (tb, qb): a start some caller would take -- its ties are not the entry's
+            qe, te = int(r[i, 1]), int(r[i, 2])
+            c = [(-cost(qe + 1), te + 1, 0), (ez1[i].mqe, te - ez1[i].mqe_t, 0), (-cost(te + 1), 0, qe + 1), (ez1[i].mte, 0, qe - ez1[i].mte_q)]
+            best = max(c, key=lambda x: x[0])
+            sc.append(best[0]); st.append(best[1:])
+        live = [i for i in range(n) if st[i][0] <= r[i, 2] and st[i][1] <= r[i, 1]]
+        b2 = lib.make_batch([q[i][st[i][1]:r[i, 1] + 1] for i in live], [t[i][st[i][0]:r[i, 2] + 1] for i in live], mat, gapo, gape, w=-1, zdrop=-1, flag=GENERIC_SC)
+        ez2 = (ksw2_amd.KswExtz * max(len(live), 1))()
+        t4 = time.perf_counter()
+        rc |= L.ksw2amd_extz_batch(None, ctypes.byref(b2.sc), len(live), b2.pairs, ez2)
+        t5 = time.perf_counter()
+        hand.update(score=sc, fwd=r, global_ok=all(ez2[k].score == sc[i] for k, i in enumerate(live)),
+                    lib_s=hand.get("lib_s", []) + [(t1 - t0) + (t3 - t2) + (t5 - t4)], host_s=hand.get("host_s", []) + [(t2 - t1) + (t4 - t3)])
+        for k in range(len(live)):
+            ksw2_amd._libc.free(ctypes.cast(ez2[k].cigar, ctypes.c_void_p))
+        return rc
+
+    fns = dict(sga_coords=lambda: L.ksw2amd_sg_align_batch(None, 5, mpp, gapo, gape, SCORE_ONLY, n, pairs, alns["sga_coords"]),
+               sgda_coords=lambda: L.ksw2amd_sgd_align_batch(None, 5, mpp, gapo, gape, go2, ge2, SCORE_ONLY, n, pairs, alns["sgda_coords"]),
+               ova_coords=lambda: L.ksw2amd_ov_align_batch(None, 5, mpp, gapo, gape, ends, SCORE_ONLY, n, pairs, alns["ova_coords"]),
+               ovda_coords=lambda: L.ksw2amd_ovd_align_batch(None, 5, mpp, gapo, gape, go2, ge2, ends, SCORE_ONLY, n, pairs, alns["ovda_coords"]),
+               ova_cigar=lambda: L.ksw2amd_ov_align_batch(None, 5, mpp, gapo, gape, ends, 0, n, pairs, alns["ova_cigar"]),
+               by_hand=by_hand)
+    tags = dict(sga_coords="sga", sgda_coords="sgda", ova_coords="ova", ovda_coords="ovda", ova_cigar="ova", by_hand="ov: pairs")
+    forms = {}
+    os.environ["KSW2AMD_TRACE"] = "1"                          # the warm-ups' form lines
+    for name, fn in fns.items():
+        err_fd = os.dup(2)
+        with open(os.devnull if a.out is None else a.out + ".trace", "w+") as tr:
+            os.dup2(tr.fileno(), 2)
+            try:
+                rc = fn()
+            finally:
+                os.dup2(err_fd, 2)
+                os.close(err_fd)
+            tr.seek(0)
+            forms[name] = [re.sub(r"^\[ksw2_amd\] ", "", l.strip()) for l in tr.read().splitlines() if "] " + tags[name] in l]
+        if rc != 0:
+            raise SystemExit("library error %d: %s" % (rc, lib.last_error()))
+    os.environ.pop("KSW2AMD_TRACE")
+    hand["lib_s"], hand["host_s"] = [], []                     # (the warm-up's)
+    times = {k: [] for k in fns}
+    for _ in range(a.reps):                                    # alternating
+        for name, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    times["by_hand"] = hand["lib_s"]                           # the three library calls only, like the others
+    rec = dict(workload=a.workload, mode="ov-align", pairs=n, cells=cells, ll_form=form, ends=ends, costs2=[go2, ge2], pairs_turned_round=int(sum(swap)),
+               clock="library calls only: pair and result arrays are built before them; the six alternate batch by batch; by_hand = the sum of "
+                     "its three library calls, the host reversal and the pair arrays between them in by_hand_host_s")
+    for name in fns:
+        ts = times[name]
+        rec[name] = dict(e2e_s=min(ts), e2e_all_s=ts, e2e_spread=(max(ts) - min(ts)) / min(ts), pairs_per_s=n / min(ts), e2e_gcups=cells / min(ts) / 1e9,
+                         forms=forms[name][:4])
+    rec["by_hand_host_s"] = hand["host_s"]
+    al = alns["ova_cigar"]
+    rec["empty_target_intervals"] = int(sum(al[i].tb > al[i].te for i in range(n)))
+    rec["empty_query_intervals"] = int(sum(al[i].qb > al[i].qe for i in range(n)))
+    rec["starts_in_row_0"] = int(sum(al[i].qb > 0 for i in range(n)))
+    rec["mean_target_interval"] = float(np.mean([al[i].te - al[i].tb + 1 for i in range(n)]))
+    rec["mean_rectangle_cells"] = float(np.mean([(al[i].te + 1) * (al[i].qe + 1) for i in range(n)]))
+    rec["by_hand_agrees"] = bool(hand["global_ok"] and all(hand["score"][i] == al[i].score and hand["fwd"][i, 1] == al[i].qe and hand["fwd"][i, 2] == al[i].te
+                                                          for i in range(n)))
+    idx = np.linspace(0, n - 1, a.parity).astype(int)
+    F = ("score", "qb", "qe", "tb", "te")
+    rec["parity_sample"] = int(len(idx))
+    rec["parity_ok"] = True
+    for key, costs in (("ova_coords", (gapo, gape)), ("ova_cigar", (gapo, gape)), ("ovda_coords", (gapo, gape, go2, ge2))):
+        exp = ova.oracle_cells([q[i] for i in idx], [t[i] for i in idx], mat, costs, ends, 5)
+        rec["parity_ok"] = bool(rec["parity_ok"] and all(tuple(exp[k]) == tuple(getattr(alns[key][i], f) for f in F) for k, i in enumerate(idx)))
+    if a.ktrace:
+        def nl(line):
+            return sum(int(x) > 0 for x in re.findall(r"(?:pk|int32)_tasks=(\d+)", line))
+        per = nl(forms["ova_coords"][0])
+        k = {name: trace_batches(a.ktrace, "k2a_%s_kernel" % name, per) for name in ("sg", "sg_rev", "sgd", "sgd_rev", "ov", "ov_rev", "ovd", "ovd_rev")}
+        skip = dict(sg_rev=1, sgd_rev=1, ov_rev=2, ovd_rev=1)  # the warm-ups
+        kr = {name: k[name][skip[name]:] for name in skip}
+        spread = lambda x: (max(x) - min(x)) / min(x) if x else None
+        mean = lambda x: sum(x) / len(x) if x else None
+        rec["kernel"] = dict({name + "_kernel_ms": v for name, v in kr.items()}, **{name + "_spread": spread(v) for name, v in kr.items()})
+        rec["kernel"].update(sg_kernel_ms=k["sg"][1:], sgd_kernel_ms=k["sgd"][1:], ov_kernel_ms=k["ov"][3:], ovd_kernel_ms=k["ovd"][1:],
+                             ov_rev_over_sg_rev=mean(kr["ov_rev"]) / mean(kr["sg_rev"]) if kr["ov_rev"] and kr["sg_rev"] else None,
+                             ovd_rev_over_sgd_rev=mean(kr["ovd_rev"]) / mean(kr["sgd_rev"]) if kr["ovd_rev"] and kr["sgd_rev"] else None,
+                             ov_rev_over_ov=mean(kr["ov_rev"]) / mean(k["ov"][3:]) if kr["ov_rev"] and k["ov"][3:] else None)
+    for x in alns["ova_cigar"]:
+        ksw2_amd._libc.free(ctypes.cast(x.cigar, ctypes.c_void_p))
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as fo:
+            json.dump(rec, fo, indent=1)
+    return 0 if rec["parity_ok"] and rec["by_hand_agrees"] else 1
+
+
 def main_sgd(a, lib, q, t, mat, gapo, gape, cells, form):
     """--sgd / --sgd-align: the two-piece semi-global entries beside ksw2amd_lld_batch (and ksw2amd_sg_batch), alternating"""
     from tests import sgd_util as sd
@@ -833,6 +969,7 @@ def main():
     ap.add_argument("--sgd", action="store_true", help="ksw2amd_sgd_batch under (4, 2, 24, 1) beside ksw2amd_lld_batch and ksw2amd_sg_batch on the pair array of --sg, alternating, library calls only in the clock")
     ap.add_argument("--sgd-align", action="store_true", help="ksw2amd_lld_batch and ksw2amd_sgd_align_batch (SCORE_ONLY and with CIGARs) on the same pair array, alternating")
     ap.add_argument("--ov", action="store_true", help="ksw2amd_ov_batch with both query ends free beside ksw2amd_ll_batch and ksw2amd_sg_batch on the pair array of --sg, alternating, library calls only in the clock")
+    ap.add_argument("--ov-align", action="store_true", help="ksw2amd_sg_align_batch / sgd / ov / ovd with SCORE_ONLY, ksw2amd_ov_align_batch with CIGARs and the by-hand pattern (ov_batch, host reversal, two ksw2amd_extz_batch calls) on the pair array of --sg, alternating")
     ap.add_argument("--excl", type=int, default=-1, help="with --sub: the excluded rows on either side of te (-1: ceil(score / smax))")
     ap.add_argument("--ktrace", default=None, help="with --sub: kernel_trace.csv of a rocprofv3 --kernel-trace run of the same command")
     ap.add_argument("--pairs", type=int, default=0, help="only the first N pairs of the workload")
@@ -849,6 +986,8 @@ def main():
     if form is not None:
         os.environ["KSW2AMD_LL_FORM"] = form
     lib = ksw2_amd.library()
+    if a.ov_align:
+        return main_ov_align(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.ov:
         return main_ov(a, lib, q, t, mat, gapo, gape, cells, form)
     if a.sgd or a.sgd_align:
